@@ -20,6 +20,26 @@ chain steps/s / hot share caps this workload on any N.  BASELINE configs[3]
 routed and as key-shard replicas (each rank its own keys, no data-path
 collective), in `secondary`.
 
+A plain run does what the headline needs and no more: it sets up, warms up,
+times `--steps` steps and prints the line (the replay kernel's event times, the
+roofline and the engine's counters are read off the timed steps themselves).
+`--full` adds every measurement that takes work of its own: the latency phase
+and the per-stage breakdown (further batches after the timed region), the CPU
+baselines, and on N > 1 the configs[3] secondaries.
+
+The trace's first 64 batches are generated on the host (the generators are
+seeded: the same arguments give the same inputs on every run).  A run with more
+steps than that replays the pool: step b takes batch b mod 64 moved b // 64
+passes later in time, so per-key time still never goes backwards; such a step
+costs 8 bytes of HBM per request (its own timestamps) and no host time.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller,
+one DIR/<name>.npy per output array (decision as float32; remaining,
+retry_after_ns, reset_at_ns_minus_t0 and tokens as float64).  reset_at_ns is
+stored less the trace's start T0 = 1.76e18 ns, which float64 holds exactly;
+tokens is 0 where the request's config is no token bucket.  A batch too large
+for 64 MB is cut to a fixed, seeded sample of its rows (sample_index.npy).
+
 Prints one JSON line (rank 0).
 """
 from __future__ import annotations
@@ -244,6 +264,59 @@ KEYSPACE = {"tb_zipf": (1 << 21, 1024), "tb_zipf15": (1 << 21, 1024), "tb_hot": 
             "fw_uniform": (1024, 1 << 15), "sw_bursty": (1024, 1 << 27), "mixed": (1 << 26, 1 << 26)}
 
 
+TRACE_POOL = 64              # batches of the trace generated on the host (steps past them replay the pool)
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: all arrays together stay under 64 MB
+
+
+def trace_pool(gen, nb):
+    """the trace's first min(nb, TRACE_POOL) batches and the time they span"""
+    import traces
+    pool = [gen.next_batch() for _ in range(min(nb, TRACE_POOL))]
+    return pool, gen.t - traces.T0
+
+
+def resident_steps(batches, pool_n, nb, span, dev):
+    """The device batches in step order.  `batches`: (key, ts, n, cfg) device
+    tensors of the pool (the first pool_n) and of the batches that follow the
+    timed region.  Step b < nb is pool batch b mod pool_n moved b // pool_n
+    spans later in time (key, n and cfg shared, timestamps of its own, all
+    made here, before any timing); the batches after the timed region move by
+    the last step's shift, so time never goes backwards."""
+    import torch
+    steps = list(batches[:pool_n])
+    rows = nb - pool_n
+    if rows > 0:
+        m = batches[0][1].numel()
+        free = torch.cuda.mem_get_info(dev)[0] if dev.type == "cuda" else float("inf")
+        if rows * m * 8 > 0.8 * free:
+            raise SystemExit(f"--steps: {rows} steps past the {pool_n}-batch pool need {rows * m * 8 / 1e9:.0f} GB "
+                             f"for their timestamps, {free / 1e9:.0f} GB are free")
+        b = torch.arange(pool_n, nb, device=dev)
+        later = torch.stack([t for _, t, _, _ in batches[:pool_n]])[b % pool_n]
+        later += (torch.div(b, pool_n, rounding_mode="floor") * span).unsqueeze(1)
+        for i in range(rows):
+            k, _, n, c = batches[i % pool_n]
+            steps.append((k, later[i], n, c))
+    shift = (max(nb, 1) - 1) // pool_n * span
+    return steps + [(k, t + shift if shift else t, n, c) for k, t, n, c in batches[pool_n:]]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy per output array of the last timed step
+    (name -> device tensor of one value per request), float32 / float64"""
+    os.makedirs(path, exist_ok=True)
+    m = next(iter(arrays.values())).numel()
+    per_row = sum(4 if t.dtype.itemsize == 1 else 8 for t in arrays.values())
+    idx = None
+    if m * per_row > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(m, DUMP_MAX_BYTES // (per_row + 8), replace=False))
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        a = a if idx is None else a[idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64))
+
+
 REHEARSE = [False]     # --rehearse-gloo (main)
 CDEV = [None]          # device of the small collective tensors: the GPU (RCCL), the CPU (gloo)
 
@@ -319,11 +392,15 @@ def bench_local(args, workload, world, rank, local_rank, dev, sharded):
     import torch.distributed as dist
 
     import rl_amd
+    from traces import T0
     gen = make_workload(workload, args.batch, rank)
     nb = args.warmup + args.steps
-    lat_n = max(0, args.lat_batches) if world == 1 else 0
-    extra = lat_n if lat_n else 4      # batches after the timed region (latency / stage breakdown)
-    host = [gen.next_batch() for _ in range(nb + extra)]
+    lat_n = max(0, args.lat_batches) if world == 1 and args.full else 0
+    # --full: batches after the timed region (latency / stage breakdown)
+    extra = (lat_n if lat_n else 4) if args.full else 0
+    host, span = trace_pool(gen, nb)
+    pool_n = len(host)
+    host += [gen.next_batch() for _ in range(extra)]
     if os.environ.get("RL_BENCH_HOME_SORT"):
         # A/B experiment only: each batch stably reordered by the key's home
         # slot in the engine's tables ("full") or by its top 8 bits ("digit"),
@@ -356,6 +433,9 @@ def bench_local(args, workload, world, rank, local_rank, dev, sharded):
             torch.from_numpy(n).to(dev),
             torch.from_numpy(cfg.view(np.int32)).to(dev),
         ))
+    dev_batches = resident_steps(dev_batches, pool_n, nb, span, dev)
+    # the host batch behind step b (the steps past the pool replay it)
+    host_of = [b % pool_n for b in range(nb)] + list(range(pool_n, pool_n + extra))
     key_strings = []
     if args.string_keys:
         # fixed-width raw keys 'user:RR:xxxxxxxxxxxx' (20 B), built vectorized
@@ -394,7 +474,7 @@ def bench_local(args, workload, world, rank, local_rank, dev, sharded):
         k, t, n, c = dev_batches[b]
         if args.string_keys:
             # raw keys: hashed on the engine's grouping stream ahead of the probe
-            raw, off, _ = key_strings[b]
+            raw, off, _ = key_strings[host_of[b]]
             rc = rl_amd.lib.rl_decide_batch_keys_device(
                 eng.h, m, raw.data_ptr(), raw.numel(), off.data_ptr(), 1, b"ratelimit", 9, t.data_ptr(),
                 n.data_ptr(), c.data_ptr(), None, out_dec.data_ptr(), out_rem.data_ptr(), out_retry.data_ptr(),
@@ -452,7 +532,14 @@ def bench_local(args, workload, world, rank, local_rank, dev, sharded):
                           "replay_us_mean": float(np.mean(us[:, 3] - us[:, 2])),
                           "replay_period_us_mean": float(np.mean(np.diff(us[:, 2]))) if len(us) > 1 else None,
                           "front_us_mean": float(np.mean(us[:, 1] - us[:, 0]))}
-    eng.set_timing(2)   # every stage, for the breakdown
+    if args.dump_outputs and rank == 0:
+        # the out_* arrays still hold the last timed step's results
+        tbc = torch.tensor([a == 1 for a, _, _ in gen.configs], device=dev)
+        is_tb = tbc[dev_batches[nb - 1][3].long()]
+        dump_outputs(args.dump_outputs, {
+            "decision": out_dec, "remaining": out_rem, "retry_after_ns": out_retry,
+            "reset_at_ns_minus_t0": out_reset - T0, "tokens": torch.where(is_tb, out_tok, 0.0)})
+    eng.set_timing(2 if args.full else 0)   # every stage, for the breakdown
 
     # latency phase (p99 batch latency of the metric): the next lat_n batches of
     # the same trace, closed loop with `depth` batches in flight; a batch's
@@ -476,7 +563,7 @@ def bench_local(args, workload, world, rank, local_rank, dev, sharded):
     rc = eng.sync()
     if rc != 0:
         raise SystemExit(f"engine error during latency phase: {rc} {eng.last_error()}")
-    if lat_n == 0:   # no latency phase: the next few batches of the trace for the breakdown
+    if lat_n == 0 and extra:   # no latency phase: the next few batches of the trace for the breakdown
         for b in range(nb, nb + extra):
             step(b)
         torch.cuda.synchronize()
@@ -558,7 +645,7 @@ def bench_local(args, workload, world, rank, local_rank, dev, sharded):
         "hot_owner_bound": hot_owner_bound(hot_len, hot_chain_us(dbgw), m) if workload.startswith("tb_zipf")
         and not sharded else None,
         "stages_ms_per_batch": {k: v for k, v in zip(["probe", "sort", "segments", "replay", "finish"],
-                                                    (stage_ms / max(nbat, 1)).tolist())},
+                                                    (stage_ms / max(nbat, 1)).tolist())} if extra else None,
         "stages_how": "HIP events on every stream, over the latency phase (after the timed region, which "
                       "records events around the replay only)",
     }
@@ -578,7 +665,7 @@ def bench_routed(args, workload, world, rank, local_rank, dev, pg_res):
     gen = make_workload(workload, args.batch, rank)
     nb = args.warmup + args.steps
     m = args.batch
-    host = [gen.next_batch() for _ in range(nb)]
+    host, span = trace_pool(gen, nb)
     # the hot key (Zipf rank 1: every rank's generator shares the rank->id
     # permutation) in this rank's last batch, for the hot-owner bound
     hot_mine = int(np.count_nonzero(host[-1][0] == gen.keys.perm[0])) if hasattr(gen, "keys") else 0
@@ -600,6 +687,7 @@ def bench_routed(args, workload, world, rank, local_rank, dev, pg_res):
         cap = min(m, max(int(need_t.item()), int(np.ceil(1.05 * m / world))))
     ins = [(torch.from_numpy(k.view(np.int64)).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(n).to(dev),
             torch.from_numpy(c.view(np.int32)).to(dev)) for k, t, n, c in host]
+    ins = resident_steps(ins, len(host), nb, span, dev)
     del host
     algs = {a for a, _, _ in gen.configs}
     tb_cap, win_cap = KEYSPACE[workload]
@@ -647,6 +735,11 @@ def bench_routed(args, workload, world, rank, local_rank, dev, pg_res):
     dist.barrier()
     elapsed = time.perf_counter() - t0
     check("timed region")
+    if args.dump_outputs and rank == 0:
+        from traces import T0
+        dec, rem, retry, reset = outs[(args.steps - 1) % pipe.depth]
+        dump_outputs(args.dump_outputs, {"decision": dec, "remaining": rem, "retry_after_ns": retry,
+                                         "reset_at_ns_minus_t0": reset - T0})
     stage_ms, nbat = eng.stage_times()
     st = eng.stats()
     dbgw = eng.debug_words()
@@ -698,23 +791,28 @@ def main():
     ap.add_argument("--steps", type=int, default=56,
                     help="timed steps (default: batches 5-60 of the 64-batch configs[1] trace)")
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the latency phase and the per-stage breakdown "
+                         "(batches after the timed region), the CPU baselines, on N > 1 the configs[3] secondaries")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output arrays of the last timed step to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--batch", type=int, default=1_000_000)
     ap.add_argument("--workload", default="tb_zipf", choices=sorted(WORKLOAD_DESC),
                     help="default: tb_zipf (configs[1], the metric's Zipf 1M keys) on every N; on N > 1 "
                          "configs[3] (mixed, 1B keys) is reported as a named secondary metric")
     ap.add_argument("--ingress", default=None, choices=["routed", "sharded"],
                     help="N > 1: routed (default; RCCL all-to-all to the key's owner) or sharded (replicas)")
-    ap.add_argument("--no-secondary", action="store_true", help="N > 1: skip the secondary measurements")
+    ap.add_argument("--no-secondary", action="store_true", help="N > 1 with --full: skip the secondary measurements")
     ap.add_argument("--route-exchange", action="store_true",
                     help="--ingress routed at N = 1: run the loopback all-to-alls too (the N > 1 step's work)")
-    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="cpu_baseline requests per host core")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="--full: cpu_baseline requests per host core")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="N > 1 rehearsal on a one-GPU box: every rank on GPU 0, collectives over gloo (not a "
                          "measurement)")
     ap.add_argument("--no-pipeline", action="store_true", help="one batch in flight at a time")
     ap.add_argument("--lat-batches", type=int, default=32,
-                    help="batches of the latency phase (after the timed region): closed loop with the "
+                    help="--full: batches of the latency phase (after the timed region): closed loop with the "
                          "pipeline's depth in flight, per-batch issue->results-complete time")
     ap.add_argument("--string-keys", action="store_true",
                     help="requests carry raw string keys ('user:<rank>:<12 hex>'): every step runs the on-GPU "
@@ -732,6 +830,8 @@ def main():
     ap.add_argument("--grpc-frontend", choices=["native", "python"], default="native", help="--grpc server front end")
     ap.add_argument("--grpc-io-threads", type=int, default=4, help="--grpc native server event loops")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1, --warmup at least 0")
     if args.e2e:
         return e2e(args, out_fd)
     if args.grpc:
@@ -778,8 +878,9 @@ def main():
         res = bench_routed(args, workload, world, rank, local_rank, dev, pg_res)
     else:
         res = bench_local(args, workload, world, rank, local_rank, dev, sharded=world > 1)
+    args.dump_outputs = None   # the headline's outputs only
     secondary = []
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.full and not args.no_secondary:
         # configs[3] (the multi-GPU config: mixed tenants over 1B keys) routed
         # and as key-shard replicas, each under its own metric name
         for wl, ing in (("mixed", "routed"), ("mixed", "sharded")):
@@ -833,7 +934,7 @@ def main():
             out[k] = res[k]
     if secondary:
         out["secondary"] = secondary
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(workload, args.batch, args.cpu_sample)
         out["cpu_baseline"]["configs0"] = cpu_config0()
     if rank == 0:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One short bench run; prints value, stage ms and chain counters (for A/B sweeps).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-timeout -k 10 200 python bench.py --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline ${BARGS:-} > /tmp/bb.json || exit $?
+timeout -k 10 200 python bench.py --full --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline ${BARGS:-} > /tmp/bb.json || exit $?
 python - "${TAG:-}" <<'PY'
 import json, sys
 d = json.load(open("/tmp/bb.json"))

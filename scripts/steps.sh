@@ -29,12 +29,12 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=$1
 shift
 F=$(mktemp /tmp/steps.XXXXXX)
-B="--steps 20 --warmup 5 --no-cpu-baseline --lat-batches 0"
+B="--full --steps 20 --warmup 5 --no-cpu-baseline --lat-batches 0"
 while [ $# -gt 0 ]; do
     case "$1" in
     gpu) echo "${TAG}_gpu 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread" ;;
     smoke) echo "${TAG}_smoke 200 python -u -c \"import __graft_entry__ as g; g.smoke()\"" ;;
-    bench) echo "${TAG}_bench 300 python -u bench.py --gpus 1 --steps 20 --warmup 5" ;;
+    bench) echo "${TAG}_bench 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full" ;;
     survey | hot | routed)
         if [ "$1" = survey ]; then
             echo "${TAG}_mixed 240 python -u bench.py --workload mixed $B"

@@ -8,7 +8,7 @@ for r in $RUNS; do
   wl=${r%%:*}; ing=${r#*:}
   name=$wl${ing:+_$ing}
   extra=""; [ -n "$ing" ] && extra="--ingress $ing"
-  timeout -k 10 240 python bench.py --workload $wl $extra --steps ${STEPS:-12} --warmup 3 --no-cpu-baseline \
+  timeout -k 10 240 python bench.py --full --workload $wl $extra --steps ${STEPS:-12} --warmup 3 --no-cpu-baseline \
       --lat-batches 0 ${BARGS:-} > gpurun_out/survey/$name.json 2> gpurun_out/survey/$name.err
   rc=$?
   if [ $rc -ne 0 ]; then echo "$name rc=$rc"; tail -5 gpurun_out/survey/$name.err; [ $rc -ge 124 ] && exit $rc; continue; fi
