@@ -490,6 +490,15 @@ __device__ __attribute__((always_inline)) inline void ch_produce_x(ChainShared& 
     // and the test's own conversions and subtractions add under 512.  A tile
     // that reaches 2^60 anywhere gets slack -inf: it is never committed, the
     // chain replays it exactly.
+    //
+    // No trace reaches this guard: it is a defence, not a path.  A window gets
+    // here only through ch_plan / ch_plan_par, with vt from the plan.  The
+    // plan's envelope [lo, hi] holds every tile start and, a tile's positive
+    // and negative parts being added separately, every prefix inside a tile.
+    // With m = max(|lo|, |hi|), Et = floor(log10 m) and F = max(Et - 4,
+    // XDEC_FMIN), every |V| <= m 10^(13 - F) < 10^(Et + 1) 10^(17 - Et) = 1e18
+    // < 2^60 (less still when F is held at XDEC_FMIN).  An add dropped above
+    // (2^62 scaled) would alone put m 10^(13 - F) past 2e18: no such plan.
     double ymin = __builtin_inf(), slack = fabs(Vl) < 0x1p60 && fabs(vt * PF) < 0x1p60 ? __builtin_inf()
                                                                                         : -__builtin_inf();
     double dev = 0.0;
