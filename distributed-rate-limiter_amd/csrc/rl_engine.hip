@@ -26,8 +26,10 @@
 #include "../../include/rl_engine.h"
 #include "../../include/rl_keyhash.h"
 #include "../../include/rl_route.h"
+#include "../../include/rl_snapshot.h"
 #include "rl_replay.h"
 #include "rl_semantics.h"
+#include "rl_snapshot.h"
 #include "rl_sort.h"
 #include "rl_table.h"
 
@@ -1586,66 +1588,231 @@ extern "C" int rl_table_keys(rl_engine* e, int64_t now_ms, rl_key_rec* out, size
     return RL_OK;
 }
 
-extern "C" int rl_table_gc(rl_engine* e, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
-                           rl_table_info* out) {
-    if (!e || (out && out->struct_size < 8)) return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    const uint64_t tb_cap = tb_capacity ? pow2_at_least(std::max<uint64_t>(tb_capacity, 1024)) : e->tb_cap;
-    const uint64_t win_cap = win_capacity ? pow2_at_least(std::max<uint64_t>(win_capacity, 1024)) : e->win_cap;
-    const uint64_t spill_cap = e->spill_follows ? pow2_at_least(std::max<uint64_t>(2 * win_cap, 1024)) : e->spill_cap;
-    if (tb_cap + win_cap >= (1ull << 31)) return fail(e, RL_EINVAL, "table capacities too large");
+// A table rebuild: fresh tables that receive the live state and then replace
+// the engine's.  rl_table_gc and rl_snapshot_import share every step, so what
+// follows the capacities (slot ids, sort bits) cannot drift between them.
+struct Rebuild {
+    TbEntry* tb = nullptr;
+    WinEntry* win = nullptr;
+    SpillEntry* sp = nullptr;
+    uint64_t tb_cap = 0, win_cap = 0, spill_cap = 0;
+    // [0..5] the engine's own tables (live, lost per table); from REBUILD_IMPORT
+    // on, four words per imported section (rl_snapshot.h SNAP_LIVE..)
+    unsigned long long* d = nullptr;
+};
+constexpr int REBUILD_IMPORT = 6;
+constexpr int REBUILD_WORDS = REBUILD_IMPORT + 3 * 4;
+
+static void rebuild_abort(Rebuild& R) {
+    (void)hipFree(R.tb);
+    (void)hipFree(R.win);
+    (void)hipFree(R.sp);
+    (void)hipFree(R.d);
+    R = Rebuild{};
+}
+
+// capacities (0 = keep; rounding and limits), drain, allocate and initialise
+// the fresh tables, and enqueue the rehash of the engine's live state at
+// now_ms on the engine's stream (not waited for)
+static int rebuild_begin(rl_engine* e, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity, Rebuild& R,
+                         const char* what) {
+    R.tb_cap = tb_capacity ? pow2_at_least(std::max<uint64_t>(tb_capacity, 1024)) : e->tb_cap;
+    R.win_cap = win_capacity ? pow2_at_least(std::max<uint64_t>(win_capacity, 1024)) : e->win_cap;
+    R.spill_cap = e->spill_follows ? pow2_at_least(std::max<uint64_t>(2 * R.win_cap, 1024)) : e->spill_cap;
+    if (R.tb_cap + R.win_cap >= (1ull << 31)) return fail(e, RL_EINVAL, "table capacities too large");
     int r = drain(e);
     if (r != RL_OK) return r;
-    TbEntry* ntb = nullptr;
-    WinEntry* nwin = nullptr;
-    SpillEntry* nsp = nullptr;
-    unsigned long long* d = nullptr;
-    bool ok = hipMalloc(&ntb, sizeof(TbEntry) * tb_cap) == hipSuccess;
-    ok = ok && hipMalloc(&nwin, sizeof(WinEntry) * win_cap) == hipSuccess;
-    ok = ok && hipMalloc(&nsp, sizeof(SpillEntry) * spill_cap) == hipSuccess;
-    ok = ok && hipMalloc(&d, 6 * sizeof(unsigned long long)) == hipSuccess;
+    bool ok = hipMalloc(&R.tb, sizeof(TbEntry) * R.tb_cap) == hipSuccess;
+    ok = ok && hipMalloc(&R.win, sizeof(WinEntry) * R.win_cap) == hipSuccess;
+    ok = ok && hipMalloc(&R.sp, sizeof(SpillEntry) * R.spill_cap) == hipSuccess;
+    ok = ok && hipMalloc(&R.d, REBUILD_WORDS * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) {
-        (void)hipFree(ntb); (void)hipFree(nwin); (void)hipFree(nsp); (void)hipFree(d);
-        return fail(e, RL_ENOMEM, "table gc: allocation failed");
+        rebuild_abort(R);
+        return fail(e, RL_ENOMEM, std::string(what) + ": allocation failed");
     }
-    unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
     hipStream_t s = e->stream;
-    k_init_tb<<<2048, 256, 0, s>>>(ntb, tb_cap);
-    k_init_win<<<2048, 256, 0, s>>>(nwin, win_cap);
-    k_init_spill<<<2048, 256, 0, s>>>(nsp, spill_cap);
-    ok = hipMemsetAsync(d, 0, sizeof h, s) == hipSuccess;
-    k_rehash<<<2048, 256, 0, s>>>(e->d_tb, e->tb_cap, ntb, tb_cap - 1, now_ms, e->profile, d);
-    k_rehash<<<2048, 256, 0, s>>>(e->d_win, e->win_cap, nwin, win_cap - 1, now_ms, e->profile, d + 2);
-    // after the window entries: each live spill entry is counted in its new entry
-    k_spill_rehash<<<2048, 256, 0, s>>>(e->d_spill, e->spill_cap, nsp, spill_cap - 1, nwin, win_cap - 1, now_ms,
-                                        e->profile, d + 4);
-    ok = ok && hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s) == hipSuccess;
-    ok = ok && hipStreamSynchronize(s) == hipSuccess;
-    (void)hipFree(d);
-    if (!ok || h[1] || h[3] || h[5]) {
-        (void)hipFree(ntb);
-        (void)hipFree(nwin);
-        (void)hipFree(nsp);
-        return ok ? fail(e, RL_ENOMEM, "table gc: live keys do not fit the requested capacity")
-                  : fail(e, RL_EDEVICE, "table gc failed");
+    k_init_tb<<<2048, 256, 0, s>>>(R.tb, R.tb_cap);
+    k_init_win<<<2048, 256, 0, s>>>(R.win, R.win_cap);
+    k_init_spill<<<2048, 256, 0, s>>>(R.sp, R.spill_cap);
+    if (hipMemsetAsync(R.d, 0, REBUILD_WORDS * sizeof(unsigned long long), s) != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        rebuild_abort(R);
+        return fail(e, RL_EDEVICE, std::string(what) + " failed");
     }
+    k_rehash<<<2048, 256, 0, s>>>(e->d_tb, e->tb_cap, R.tb, R.tb_cap - 1, now_ms, e->profile, R.d);
+    k_rehash<<<2048, 256, 0, s>>>(e->d_win, e->win_cap, R.win, R.win_cap - 1, now_ms, e->profile, R.d + 2);
+    // after the window entries: each live spill entry is counted in its new entry
+    k_spill_rehash<<<2048, 256, 0, s>>>(e->d_spill, e->spill_cap, R.sp, R.spill_cap - 1, R.win, R.win_cap - 1, now_ms,
+                                        e->profile, R.d + 4);
+    return RL_OK;
+}
+
+// wait for the rebuild's kernels and read its counters
+static bool rebuild_finish(rl_engine* e, Rebuild& R, unsigned long long (&h)[REBUILD_WORDS]) {
+    hipStream_t s = e->stream;
+    bool ok = hipMemcpyAsync(h, R.d, sizeof h, hipMemcpyDeviceToHost, s) == hipSuccess;
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
+    return ok;
+}
+
+// the fresh tables become the engine's
+static void rebuild_commit(rl_engine* e, Rebuild& R) {
     (void)hipFree(e->d_tb);
     (void)hipFree(e->d_win);
     (void)hipFree(e->d_spill);
-    e->d_tb = ntb;
-    e->d_win = nwin;
-    e->d_spill = nsp;
+    (void)hipFree(R.d);
+    e->d_tb = R.tb;
+    e->d_win = R.win;
+    e->d_spill = R.sp;
     // slot ids (the sort keys) follow the capacities
-    e->tb_cap = tb_cap;
-    e->win_cap = win_cap;
-    e->spill_cap = spill_cap;
-    e->win_base = (uint32_t)tb_cap;
-    e->invalid_key = (uint32_t)(tb_cap + win_cap);
+    e->tb_cap = R.tb_cap;
+    e->win_cap = R.win_cap;
+    e->spill_cap = R.spill_cap;
+    e->win_base = (uint32_t)R.tb_cap;
+    e->invalid_key = (uint32_t)(R.tb_cap + R.win_cap);
     e->sort_bits = bitlen(e->invalid_key);
     e->sort_passes = (e->sort_bits + 7) / 8;
     e->sort_shifts = sort_shifts(e->sort_bits, e->sort_passes);
     e->stats.sort_bits = e->sort_bits;
     e->stats.sort_passes = e->sort_passes;
+    R = Rebuild{};
+}
+
+extern "C" int rl_table_gc(rl_engine* e, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
+                           rl_table_info* out) {
+    if (!e || (out && out->struct_size < 8)) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    Rebuild R;
+    int r = rebuild_begin(e, now_ms, tb_capacity, win_capacity, R, "table gc");
+    if (r != RL_OK) return r;
+    unsigned long long h[REBUILD_WORDS];
+    const bool ok = rebuild_finish(e, R, h);
+    if (!ok || h[1] || h[3] || h[5]) {
+        rebuild_abort(R);
+        return ok ? fail(e, RL_ENOMEM, "table gc: live keys do not fit the requested capacity")
+                  : fail(e, RL_EDEVICE, "table gc failed");
+    }
+    rebuild_commit(e, R);
+    return out ? rl_table_info_get(e, now_ms, out) : RL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// snapshots (include/rl_snapshot.h)
+// ---------------------------------------------------------------------------
+
+static rl_snapshot_info snapshot_info_of(const SnapHeader& h) {
+    return rl_snapshot_info{sizeof(rl_snapshot_info), h.version, h.profile, h.world, h.rank, 0, h.now_ms,
+                            h.tb_count, h.win_count, h.spill_count, h.total, h.payload_sum};
+}
+
+extern "C" int rl_snapshot_inspect(const void* buf, size_t len, rl_snapshot_info* out) {
+    if (!out || out->struct_size < 8) return RL_EINVAL;
+    SnapHeader h;
+    if (!snap_header_ok(buf, len, &h) || !snap_payload_ok(buf, h)) return RL_EINVAL;
+    return copy_out(out, snapshot_info_of(h));
+}
+
+extern "C" int rl_snapshot_export(rl_engine* e, int64_t now_ms, uint32_t world, uint32_t rank, void* buf, size_t cap,
+                                  rl_snapshot_info* out) {
+    if (!e || !out || out->struct_size < 8 || (!buf && cap)) return RL_EINVAL;
+    if (world == 0 || rank >= world) return fail(e, RL_EINVAL, "snapshot export: rank outside the world");
+    (void)hipSetDevice(e->device);
+    int r = drain(e);
+    if (r != RL_OK) return r;
+    hipStream_t s = e->stream;
+    unsigned long long* d = e->d_count;
+    unsigned long long* h = e->h_count;
+    // the live size first (count and checksum, no writes): nothing runs on
+    // the drained engine, so the writing launch finds the same records
+    bool ok = hipMemsetAsync(d, 0, SNAP_WORDS * sizeof(unsigned long long), s) == hipSuccess;
+    k_snapshot_export<false><<<2048, SNAP_BLOCK, 0, s>>>(e->d_tb, e->tb_cap, e->d_win, e->win_cap, e->d_spill,
+                                                         e->spill_cap, now_ms, e->profile, world, rank, nullptr, 0,
+                                                         nullptr, 0, nullptr, 0, d);
+    ok = ok && hipMemcpyAsync(h, d, SNAP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) == hipSuccess;
+    ok = ok && hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) return fail(e, RL_EDEVICE, "snapshot export: count failed");
+    const SnapHeader hd = snap_make_header(e->profile, h[SNAP_TB], h[SNAP_WIN], h[SNAP_SPILL], now_ms, world, rank,
+                                           h[SNAP_SUM]);
+    r = copy_out(out, snapshot_info_of(hd));
+    if (r != RL_OK || !buf) return r;
+    if (cap < hd.total) return fail(e, RL_ENOMEM, "snapshot export: buffer too small");
+    const size_t payload = hd.total - sizeof hd;
+    if (payload) {
+        uint8_t* stage = nullptr;
+        if (hipMalloc(&stage, payload) != hipSuccess) return fail(e, RL_ENOMEM, "snapshot export: allocation failed");
+        const size_t tb_end = hd.tb_off + sizeof(TbEntry) * hd.tb_count;
+        ok = hipMemsetAsync(d, 0, SNAP_WORDS * sizeof(unsigned long long), s) == hipSuccess;
+        if (hd.win_off > tb_end)   // the padding in front of the window section
+            ok = ok && hipMemsetAsync(stage + (tb_end - sizeof hd), 0, hd.win_off - tb_end, s) == hipSuccess;
+        k_snapshot_export<true><<<2048, SNAP_BLOCK, 0, s>>>(
+            e->d_tb, e->tb_cap, e->d_win, e->win_cap, e->d_spill, e->spill_cap, now_ms, e->profile, world, rank,
+            (TbEntry*)(stage + (hd.tb_off - sizeof hd)), hd.tb_count, (WinEntry*)(stage + (hd.win_off - sizeof hd)),
+            hd.win_count, (SpillEntry*)(stage + (hd.spill_off - sizeof hd)), hd.spill_count, d);
+        ok = ok && hipMemcpyAsync(h, d, SNAP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) == hipSuccess;
+        ok = ok && hipStreamSynchronize(s) == hipSuccess;
+        ok = ok && h[SNAP_TB] == hd.tb_count && h[SNAP_WIN] == hd.win_count && h[SNAP_SPILL] == hd.spill_count &&
+             h[SNAP_SUM] == hd.payload_sum;
+        ok = ok && hipMemcpy((uint8_t*)buf + sizeof hd, stage, payload, hipMemcpyDeviceToHost) == hipSuccess;
+        (void)hipFree(stage);
+        if (!ok) return fail(e, RL_EDEVICE, "snapshot export failed");
+    }
+    memcpy(buf, &hd, sizeof hd);
+    return RL_OK;
+}
+
+extern "C" int rl_snapshot_import(rl_engine* e, const void* buf, size_t len, int64_t now_ms, uint64_t tb_capacity,
+                                  uint64_t win_capacity, rl_table_info* out) {
+    if (!e || (out && out->struct_size < 8)) return RL_EINVAL;
+    SnapHeader hd;
+    if (!snap_header_ok(buf, len, &hd)) return fail(e, RL_EINVAL, "snapshot import: bad header");
+    if (hd.profile != e->profile) return fail(e, RL_EINVAL, "snapshot import: taken under the other profile");
+    (void)hipSetDevice(e->device);
+    const size_t payload = hd.total - sizeof hd;
+    uint8_t* stage = nullptr;
+    if (payload && hipMalloc(&stage, payload) != hipSuccess)
+        return fail(e, RL_ENOMEM, "snapshot import: allocation failed");
+    Rebuild R;
+    int r = rebuild_begin(e, now_ms, tb_capacity, win_capacity, R, "snapshot import");
+    if (r != RL_OK) {
+        (void)hipFree(stage);
+        return r;
+    }
+    hipStream_t s = e->stream;
+    bool ok = !payload || hipMemcpyAsync(stage, (const uint8_t*)buf + sizeof hd, payload, hipMemcpyHostToDevice, s) ==
+                              hipSuccess;
+    if (ok) {
+        unsigned long long* c = R.d + REBUILD_IMPORT;
+        k_snapshot_import<<<2048, SNAP_BLOCK, 0, s>>>((const TbEntry*)(stage + (hd.tb_off - sizeof hd)), hd.tb_count,
+                                                      R.tb, R.tb_cap - 1, now_ms, e->profile,
+                                                      (uint64_t)RL_SNAPSHOT_TAG_TB, c);
+        k_snapshot_import<<<2048, SNAP_BLOCK, 0, s>>>((const WinEntry*)(stage + (hd.win_off - sizeof hd)),
+                                                      hd.win_count, R.win, R.win_cap - 1, now_ms, e->profile,
+                                                      (uint64_t)RL_SNAPSHOT_TAG_WIN, c + 4);
+        // after the window section: a spill record is counted in its user key's new entry
+        k_snapshot_import_spill<<<2048, SNAP_BLOCK, 0, s>>>((const SpillEntry*)(stage + (hd.spill_off - sizeof hd)),
+                                                            hd.spill_count, R.sp, R.spill_cap - 1, R.win,
+                                                            R.win_cap - 1, now_ms, e->profile, c + 8);
+    }
+    unsigned long long h[REBUILD_WORDS];
+    ok = rebuild_finish(e, R, h) && ok;
+    (void)hipFree(stage);
+    const unsigned long long* c = h + REBUILD_IMPORT;
+    int code = RL_OK;
+    const char* msg = "";
+    if (!ok) {
+        code = RL_EDEVICE, msg = "snapshot import failed";
+    } else if (c[SNAP_CHECK] + c[4 + SNAP_CHECK] + c[8 + SNAP_CHECK] != hd.payload_sum) {
+        code = RL_EINVAL, msg = "snapshot import: payload checksum mismatch";
+    } else if (c[SNAP_CONFLICT] || c[4 + SNAP_CONFLICT]) {
+        code = RL_EEXIST, msg = "snapshot import: a key is in the engine and in the snapshot";
+    } else if (h[1] || h[3] || h[5] || c[SNAP_LOST] || c[4 + SNAP_LOST] || c[8 + SNAP_LOST]) {
+        code = RL_ENOMEM, msg = "snapshot import: live keys do not fit the requested capacity";
+    }
+    if (code != RL_OK) {
+        rebuild_abort(R);
+        return fail(e, code, msg);
+    }
+    rebuild_commit(e, R);
     return out ? rl_table_info_get(e, now_ms, out) : RL_OK;
 }
 

@@ -35,6 +35,7 @@ void Sub::carve(size_t m_) {
     now_ms = 0;
     cap_tb = cap_win = 0;
     info = rl_table_info{};
+    snap = SnapArgs{};
     // layout by capacity, so a reused buffer keeps its arrays in place
     const size_t c = cap;
     uint8_t* p = mem.get();
@@ -162,6 +163,16 @@ public:
     int gc(int64_t now_ms, uint64_t tb_cap, uint64_t win_cap, rl_table_info* out) override {
         (void)hipSetDevice(dev_id_);
         return rl_table_gc(e_, now_ms, tb_cap, win_cap, out);
+    }
+    int snapshot(int64_t now_ms, uint32_t world, uint32_t rank, void* buf, size_t cap,
+                 rl_snapshot_info* out) override {
+        (void)hipSetDevice(dev_id_);
+        return rl_snapshot_export(e_, now_ms, world, rank, buf, cap, out);
+    }
+    int restore(const void* buf, size_t len, int64_t now_ms, uint64_t tb_cap, uint64_t win_cap,
+                rl_table_info* out) override {
+        (void)hipSetDevice(dev_id_);
+        return rl_snapshot_import(e_, buf, len, now_ms, tb_cap, win_cap, out);
     }
     int table_of(uint32_t cfg) override {
         if (cfg >= table_.size()) {      // configs registered since: look them up once
@@ -354,10 +365,11 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
 }
 
 int Coalescer::SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
-                        uint64_t cap_win, uint64_t* ticket, void* tag) {
+                        uint64_t cap_win, uint64_t* ticket, void* tag, const SnapArgs* snap) {
     Sub* s = get_sub(1);
     s->op = op;
     s->tag = tag;
+    if (snap) s->snap = *snap;
     s->key[0] = key;
     s->ts[0] = ts;
     s->n[0] = 1;
@@ -546,8 +558,13 @@ int Coalescer::run_table_op(Sub* op) {
     int st;
     if (op->op == OP_INFO) {
         st = be_->table_info(op->now_ms, &info);
+    } else if (op->op == OP_SNAPSHOT) {
+        st = be_->snapshot(op->now_ms, op->snap.world, op->snap.rank, op->snap.buf, op->snap.len, op->snap.out);
     } else {
-        st = be_->gc(op->now_ms, op->cap_tb, op->cap_win, &info);
+        // a restore is a GC that also merges a snapshot
+        st = op->op == OP_RESTORE
+                 ? be_->restore(op->snap.buf, op->snap.len, op->now_ms, op->cap_tb, op->cap_win, &info)
+                 : be_->gc(op->now_ms, op->cap_tb, op->cap_win, &info);
         std::lock_guard<std::mutex> g(mu_);
         st_.gc_runs++;
         if (st != RL_OK) st_.gc_failures++;
@@ -664,7 +681,7 @@ void Coalescer::submitter() {
             if (pending_ == 0) continue;
         }
         Sub* f = queue_.front();
-        if (f->op == OP_INFO || f->op == OP_GC) {
+        if (is_table_op(f->op)) {
             // synchronous, on this thread: every batch before it is launched
             // and the backend drains them; nothing after it is launched yet
             queue_.pop_front();
@@ -938,9 +955,10 @@ extern "C" int rl_coalescer_reset(rl_coalescer* c, uint64_t key_id, int64_t ts_n
     return c->c->Wait(t, -1, nullptr, nullptr, nullptr, nullptr);
 }
 
-static int table_op(rl_coalescer* c, rlc::Op op, int64_t now_ms, uint64_t tb, uint64_t win, rl_table_info* out) {
+static int table_op(rl_coalescer* c, rlc::Op op, int64_t now_ms, uint64_t tb, uint64_t win, rl_table_info* out,
+                    const rlc::SnapArgs* snap = nullptr) {
     uint64_t t;
-    int rc = c->c->SubmitOp(op, 0, 0, 0, now_ms, tb, win, &t);
+    int rc = c->c->SubmitOp(op, 0, 0, 0, now_ms, tb, win, &t, nullptr, snap);
     if (rc != RL_OK) return rc;
     rl_table_info info{};
     rc = c->c->Wait(t, -1, nullptr, nullptr, nullptr, nullptr, nullptr, &info);
@@ -961,6 +979,27 @@ extern "C" int rl_coalescer_gc(rl_coalescer* c, int64_t now_ms, uint64_t tb_capa
                                rl_table_info* out) {
     if (!c || (out && out->struct_size < 8)) return RL_EINVAL;
     return table_op(c, rlc::OP_GC, now_ms, tb_capacity, win_capacity, out);
+}
+
+extern "C" int rl_coalescer_snapshot(rl_coalescer* c, int64_t now_ms, uint32_t world, uint32_t rank, void* buf,
+                                     size_t cap, rl_snapshot_info* out) {
+    if (!c || !out || out->struct_size < 8) return RL_EINVAL;
+    rlc::SnapArgs a;
+    a.buf = buf;
+    a.len = cap;
+    a.world = world;
+    a.rank = rank;
+    a.out = out;
+    return table_op(c, rlc::OP_SNAPSHOT, now_ms, 0, 0, nullptr, &a);
+}
+
+extern "C" int rl_coalescer_restore(rl_coalescer* c, const void* buf, size_t len, int64_t now_ms,
+                                    uint64_t tb_capacity, uint64_t win_capacity, rl_table_info* out) {
+    if (!c || (out && out->struct_size < 8)) return RL_EINVAL;
+    rlc::SnapArgs a;
+    a.buf = const_cast<void*>(buf);
+    a.len = len;
+    return table_op(c, rlc::OP_RESTORE, now_ms, tb_capacity, win_capacity, out, &a);
 }
 
 extern "C" int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out) {

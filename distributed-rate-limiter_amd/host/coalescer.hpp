@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/rl_coalescer.h"
+#include "../../include/rl_snapshot.h"
 
 namespace rlc {
 
@@ -58,6 +59,17 @@ public:
     // synchronous table operations (the GPU engine drains its batches first)
     virtual int table_info(int64_t now_ms, rl_table_info* out) = 0;
     virtual int gc(int64_t now_ms, uint64_t tb_cap, uint64_t win_cap, rl_table_info* out) = 0;
+    // state snapshots (include/rl_snapshot.h): the GPU engine only
+    virtual int snapshot(int64_t now_ms, uint32_t world, uint32_t rank, void* buf, size_t cap,
+                         rl_snapshot_info* out) {
+        (void)now_ms, (void)world, (void)rank, (void)buf, (void)cap, (void)out;
+        return RL_EINVAL;
+    }
+    virtual int restore(const void* buf, size_t len, int64_t now_ms, uint64_t tb_cap, uint64_t win_cap,
+                        rl_table_info* out) {
+        (void)buf, (void)len, (void)now_ms, (void)tb_cap, (void)win_cap, (void)out;
+        return RL_EINVAL;
+    }
     // the table a config's keys live in (0 token bucket, 1 window), or -1
     // when unknown (the automatic GC then counts the request against both)
     virtual int table_of(uint32_t cfg) { (void)cfg; return -1; }
@@ -66,7 +78,18 @@ public:
 std::unique_ptr<Backend> make_gpu_backend(rl_engine* e);
 std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b);
 
-enum Op : uint8_t { OP_REQ, OP_RESET, OP_INFO, OP_GC };
+enum Op : uint8_t { OP_REQ, OP_RESET, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE };
+// the synchronous table operations (run_table_op)
+inline bool is_table_op(Op op) { return op >= OP_INFO; }
+
+// OP_SNAPSHOT / OP_RESTORE arguments: the caller's buffers (it blocks until
+// the operation is done)
+struct SnapArgs {
+    void* buf = nullptr;              // OP_SNAPSHOT: written; OP_RESTORE: read
+    size_t len = 0;
+    uint32_t world = 1, rank = 0;
+    rl_snapshot_info* out = nullptr;  // OP_SNAPSHOT
+};
 
 // one submission: its requests (copied) and results, or one table operation
 struct Sub {
@@ -90,6 +113,7 @@ struct Sub {
     int64_t now_ms = 0;
     uint64_t cap_tb = 0, cap_win = 0;
     rl_table_info info{};
+    SnapArgs snap;
     std::condition_variable cv;
     std::unique_ptr<uint8_t[]> mem;
     uint64_t* key;
@@ -121,9 +145,9 @@ public:
     // tag: with SetNotify, the completion callback receives it
     int Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
                uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr);
-    // a Reset / table count / table GC, queued in sequence order
+    // a Reset / table count / table GC / snapshot / restore, queued in sequence order
     int SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
-                 uint64_t cap_win, uint64_t* ticket, void* tag = nullptr);
+                 uint64_t cap_win, uint64_t* ticket, void* tag = nullptr, const SnapArgs* snap = nullptr);
     // Completion callback for submissions made with a tag: fn(user, ticket,
     // tag) runs once when the submission is done (applied, failed, or dropped
     // unapplied), on a coalescer thread (or the thread of a Cancel / Wait that

@@ -25,6 +25,7 @@ lib = C.CDLL(LIB_PATH)
 
 # --- constants (include/rl_engine.h) -----------------------------------------
 RL_OK, RL_EINVAL, RL_ENOMEM, RL_EDEVICE, RL_ETIMEOUT, RL_EORDER = 0, -22, -12, -5, -110, -34
+RL_EEXIST = -17
 TOKEN_BUCKET, SLIDING_WINDOW, FIXED_WINDOW = 1, 2, 3
 ALG_BY_NAME = {"token_bucket": TOKEN_BUCKET, "sliding_window": SLIDING_WINDOW, "fixed_window": FIXED_WINDOW}
 PROFILE_REDIS7, PROFILE_MINIREDIS = 0, 1
@@ -90,6 +91,13 @@ class rl_table_info(_Sized):
                                           "win_live", "spill_capacity", "spill_used", "spill_live")]
 
 
+class rl_snapshot_info(_Sized):
+    """include/rl_snapshot.h"""
+    _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("profile", C.c_int32), ("world", C.c_uint32),
+                ("rank", C.c_uint32), ("pad_", C.c_uint32), ("now_ms", C.c_int64)] + [
+        (k, C.c_uint64) for k in ("tb_keys", "win_keys", "spill_keys", "bytes", "checksum")]
+
+
 class rl_coalescer_opts(_Sized):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -136,6 +144,15 @@ _sig = {
     "rl_engine_set_timing": (C.c_int, [vp, C.c_int]),
     "rl_table_info_get": (C.c_int, [vp, C.c_int64, C.POINTER(rl_table_info)]),
     "rl_table_gc": (C.c_int, [vp, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(rl_table_info)]),
+    "rl_snapshot_export": (C.c_int, [vp, C.c_int64, C.c_uint32, C.c_uint32, vp, C.c_size_t,
+                                     C.POINTER(rl_snapshot_info)]),
+    "rl_snapshot_inspect": (C.c_int, [vp, C.c_size_t, C.POINTER(rl_snapshot_info)]),
+    "rl_snapshot_import": (C.c_int, [vp, vp, C.c_size_t, C.c_int64, C.c_uint64, C.c_uint64,
+                                     C.POINTER(rl_table_info)]),
+    "rl_coalescer_snapshot": (C.c_int, [vp, C.c_int64, C.c_uint32, C.c_uint32, vp, C.c_size_t,
+                                        C.POINTER(rl_snapshot_info)]),
+    "rl_coalescer_restore": (C.c_int, [vp, vp, C.c_size_t, C.c_int64, C.c_uint64, C.c_uint64,
+                                       C.POINTER(rl_table_info)]),
     "rl_engine_stage_times": (C.c_int, [vp, vp, C.c_int, C.POINTER(C.c_uint64)]),
     "rl_last_error": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
     "rl_engine_debug_words": (C.c_int, [vp, vp, C.c_size_t]),
@@ -362,6 +379,22 @@ class Engine:
             raise EngineError(rc, self.last_error())
         return rc, out
 
+    def snapshot(self, now_ms: int, world=1, rank=0) -> np.ndarray:
+        """rl_snapshot_export (include/rl_snapshot.h): the keys live at now_ms
+        that `rank` of `world` owns, as a uint8 blob (a size query, then the
+        export into a buffer of that size)"""
+        return _snapshot(lambda buf, cap, out: lib.rl_snapshot_export(self.h, now_ms, world, rank, buf, cap, out),
+                         self.last_error)
+
+    def restore(self, blob, now_ms: int, tb_capacity=0, win_capacity=0, check=True):
+        """rl_snapshot_import: GC at now_ms plus a merge of the blob's keys"""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        out = rl_table_info()
+        rc = lib.rl_snapshot_import(self.h, _ptr(blob), blob.size, now_ms, tb_capacity, win_capacity, C.byref(out))
+        if check and rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        return rc, out
+
     def set_timing(self, level):
         """0 off, 1 replay events only, 2 every stage (True == 2), -k replay
         events on every k-th batch only (timed runs: each event pair costs the
@@ -381,6 +414,29 @@ class Engine:
         if rc != RL_OK:
             raise EngineError(rc, self.last_error())
         return out
+
+
+def _snapshot(export, last_error) -> np.ndarray:
+    """size query, then the export; `export(buf, cap, out)` is rl_snapshot_export
+    or rl_coalescer_snapshot with the leading arguments bound"""
+    info = rl_snapshot_info()
+    rc = export(None, 0, C.byref(info))
+    if rc != RL_OK:
+        raise EngineError(rc, last_error())
+    blob = np.zeros(info.bytes, np.uint8)
+    rc = export(_ptr(blob), blob.size, C.byref(info))
+    if rc != RL_OK:
+        raise EngineError(rc, last_error())
+    return blob[:info.bytes]
+
+
+def snapshot_inspect(blob):
+    """rl_snapshot_inspect: (rc, rl_snapshot_info) of a blob, checked on the
+    host (no GPU)"""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    info = rl_snapshot_info()
+    rc = lib.rl_snapshot_inspect(_ptr(blob), blob.size, C.byref(info))
+    return rc, info
 
 
 _DEDICATED_STREAMS = []   # rl_stream_create_dedicated handles (release_dedicated_streams)
@@ -750,6 +806,19 @@ class Coalescer:
     def gc(self, now_ms, tb_capacity=0, win_capacity=0):
         out = rl_table_info()
         rc = lib.rl_coalescer_gc(self.h, now_ms, tb_capacity, win_capacity, C.byref(out))
+        return rc, out
+
+    def snapshot(self, now_ms, world=1, rank=0) -> np.ndarray:
+        """rl_coalescer_snapshot: a size query, then the export, each in
+        sequence order (requests submitted in between can outgrow the buffer:
+        RL_ENOMEM)"""
+        return _snapshot(lambda buf, cap, out: lib.rl_coalescer_snapshot(self.h, now_ms, world, rank, buf, cap, out),
+                         lambda: "rl_coalescer_snapshot failed")
+
+    def restore(self, blob, now_ms, tb_capacity=0, win_capacity=0):
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        out = rl_table_info()
+        rc = lib.rl_coalescer_restore(self.h, _ptr(blob), blob.size, now_ms, tb_capacity, win_capacity, C.byref(out))
         return rc, out
 
     def stats(self) -> rl_coalescer_stats:

@@ -55,6 +55,7 @@
 #include <stdint.h>
 
 #include "rl_engine.h"
+#include "rl_snapshot.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -188,6 +189,15 @@ int rl_coalescer_reset(rl_coalescer* c, uint64_t key_id, int64_t ts_ns, uint32_t
 int rl_coalescer_table_info(rl_coalescer* c, int64_t now_ms, rl_table_info* out);
 int rl_coalescer_gc(rl_coalescer* c, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
                     rl_table_info* out);
+/* rl_snapshot_export / rl_snapshot_import (include/rl_snapshot.h) in sequence
+ * order: a snapshot sees every request submitted before it and none submitted
+ * after; a restore lands between the same two.  Block until done.  A restore
+ * counts as a GC run in the stats (it is one).  Engine-backed coalescers only:
+ * over a host backend both return RL_EINVAL. */
+int rl_coalescer_snapshot(rl_coalescer* c, int64_t now_ms, uint32_t world, uint32_t rank,
+                          void* buf, size_t cap, rl_snapshot_info* out);
+int rl_coalescer_restore(rl_coalescer* c, const void* buf, size_t len, int64_t now_ms,
+                         uint64_t tb_capacity, uint64_t win_capacity, rl_table_info* out);
 int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out);
 
 #ifdef __cplusplus

@@ -37,6 +37,7 @@ extern "C" {
 #define RL_EDEVICE    (-5)  /* HIP runtime error (text in rl_last_error) */
 #define RL_ETIMEOUT (-110)  /* a device-side bounded wait expired */
 #define RL_EORDER    (-34)  /* reserved: no longer returned (window keys of any age are kept) */
+#define RL_EEXIST (-17)  /* rl_snapshot_import: a key of the snapshot is already in the engine */
 
 /* algorithms (interface.go:11-23) */
 #define RL_ALG_TOKEN_BUCKET   1
