@@ -27,6 +27,7 @@
 #include "../../include/rl_keyhash.h"
 #include "../../include/rl_route.h"
 #include "../../include/rl_snapshot.h"
+#include "rl_peek.h"
 #include "rl_replay.h"
 #include "rl_semantics.h"
 #include "rl_snapshot.h"
@@ -617,6 +618,7 @@ struct rl_engine {
     double *s_tok = nullptr, *s_add = nullptr, *s_th = nullptr;
     hipEvent_t ev_small = nullptr;
     hipEvent_t ev_reset = nullptr;    // rl_reset_device: the DEL on `chain` -> the caller's stream
+    hipEvent_t ev_peek = nullptr;     // rl_peek_batch_device: k_peek on `chain` -> the caller's stream
     int next_set = 0, last_set = 0;   // set of the next / the last enqueued batch
     size_t zero_bytes = 0;
     int coop_grid = 128;        // k_tb_chain blocks launched (one per CU fits its LDS) ...
@@ -789,6 +791,7 @@ static void free_all(rl_engine* e) {
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     if (e->ev_small) (void)hipEventDestroy(e->ev_small);
     if (e->ev_reset) (void)hipEventDestroy(e->ev_reset);
+    if (e->ev_peek) (void)hipEventDestroy(e->ev_peek);
     for (void* p : {(void*)e->s_ts, (void*)e->s_n, (void*)e->s_sms, (void*)e->s_cfg, (void*)e->s_dec, (void*)e->s_tok,
                     (void*)e->s_add, (void*)e->s_th})
         (void)hipFree(p);
@@ -866,6 +869,7 @@ extern "C" int rl_engine_create(const rl_opts* o, rl_engine** out) {
     if (hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming) != hipSuccess) return bail(RL_EDEVICE);
     if (hipEventCreateWithFlags(&e->ev_small, hipEventDisableTiming) != hipSuccess) return bail(RL_EDEVICE);
     if (hipEventCreateWithFlags(&e->ev_reset, hipEventDisableTiming) != hipSuccess) return bail(RL_EDEVICE);
+    if (hipEventCreateWithFlags(&e->ev_peek, hipEventDisableTiming) != hipSuccess) return bail(RL_EDEVICE);
     e->small_max = SMALL_MAX;
     if (const char* v = getenv("RL_SMALL_MAX")) e->small_max = std::min<uint32_t>((uint32_t)atoi(v), SMALL_MAX);
     size_t M = e->max_batch;
@@ -1325,6 +1329,27 @@ static int run_batch(rl_engine* e, uint32_t m, ReqArgs a, hipStream_t s, bool in
     return RL_OK;
 }
 
+// enqueue one read-only query batch (rl_peek.h) of any size: k_peek on
+// `chain`, between the replays of the batches enqueued before and after it
+// (the replays -- k_tb_chain, k_replay_light, k_small -- and the DEL of a reset
+// are the only writers of entry state, all on `chain`); s waits for it.
+// No per-batch buffer is involved, and nothing is counted in rl_stats.
+static int run_peek(rl_engine* e, size_t m, ReqArgs a, hipStream_t s, bool inputs_ready) {
+    if (m == 0) return RL_OK;
+    hipStream_t c = e->chain;
+    if (!inputs_ready) {
+        HIPCHK(e, hipEventRecord(e->ev_in, s));
+        HIPCHK(e, hipStreamWaitEvent(c, e->ev_in, 0));
+    }
+    const int grid = (int)std::min<size_t>((m + PEEK_BLOCK - 1) / PEEK_BLOCK, (size_t)PEEK_GRID);
+    k_peek<<<grid, PEEK_BLOCK, 0, c>>>((uint64_t)m, a, e->d_cfg, (uint32_t)e->h_cfg.size(), e->d_tb, e->tb_cap - 1,
+                                       e->d_win, e->win_cap - 1, e->spill(), e->profile);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->ev_peek, c));
+    HIPCHK(e, hipStreamWaitEvent(s, e->ev_peek, 0));
+    return RL_OK;
+}
+
 // Launch every kernel once at creation, on batches of requests that are all
 // rejected (no config is registered yet), so no table entry is touched: HIP
 // loads kernels lazily, and a server's first batch on either path (k_small, or
@@ -1359,6 +1384,10 @@ static int warm_up(rl_engine* e) {
         ReqArgs ar{nullptr, nullptr, nullptr, nullptr, e->d_sms, nullptr, nullptr, nullptr, nullptr, nullptr};
         const RouteIn ri{nullptr, nullptr, e->d_zero, nullptr};
         const int r = run_batch(e, mb, ar, s, false, nullptr, &ri);
+        if (r != RL_OK) return r;
+    }
+    {   // the read-only query kernel
+        const int r = run_peek(e, 1, a, s, false);
         if (r != RL_OK) return r;
     }
     // the table count / GC / key listing kernels, on empty ranges: a server's
@@ -1538,6 +1567,55 @@ extern "C" int rl_reset(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t 
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return RL_OK;
 }
+
+// Read-only queries (rl_peek.h).  Ordering as rl_reset_device: one kernel on
+// `chain` is after every batch enqueued before the call and before every one
+// enqueued after it.  It raises no error flag, so the sticky status of
+// rl_engine_sync never comes from a peek.
+extern "C" int rl_peek_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                    const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                                    uint8_t* decision, int64_t* remaining, int64_t* retry_after_ns,
+                                    int64_t* reset_at_ns, double* tokens, void* stream) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !decision || !remaining || !retry_after_ns || !reset_at_ns)))
+        return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    // the grid strides over any m: no chunking
+    ReqArgs a{key_id, ts_ns, n, cfg_id, server_ms, decision, remaining, retry_after_ns, reset_at_ns, tokens};
+    return run_peek(e, m, a, s, (e->flags & RL_OPT_PIPELINE) != 0);
+}
+
+extern "C" int rl_peek_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                             const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* decision,
+                             int64_t* remaining, int64_t* retry_after_ns, int64_t* reset_at_ns, double* tokens) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !decision || !remaining || !retry_after_ns || !reset_at_ns)))
+        return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    // chunks of max_batch: the size of the host API's staging arrays
+    for (size_t off = 0; off < m; off += e->max_batch) {
+        uint32_t c = (uint32_t)std::min<size_t>(e->max_batch, m - off);
+        HIPCHK(e, hipMemcpyAsync(e->d_key, key_id + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(e->d_ts, ts_ns + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(e->d_n, n + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(e->d_cfgid, cfg_id + off, 4 * (size_t)c, hipMemcpyHostToDevice, s));
+        if (server_ms) HIPCHK(e, hipMemcpyAsync(e->d_sms, server_ms + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
+        ReqArgs a{e->d_key, e->d_ts, e->d_n, e->d_cfgid, server_ms ? e->d_sms : nullptr,
+                  e->d_dec, e->d_rem, e->d_retry, e->d_reset, tokens ? e->d_tok : nullptr};
+        // the staged inputs arrive on s: the kernel always waits for them
+        int r = run_peek(e, c, a, s, false);
+        if (r != RL_OK) return r;
+        HIPCHK(e, hipMemcpyAsync(decision + off, e->d_dec, c, hipMemcpyDeviceToHost, s));
+        HIPCHK(e, hipMemcpyAsync(remaining + off, e->d_rem, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
+        HIPCHK(e, hipMemcpyAsync(retry_after_ns + off, e->d_retry, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
+        HIPCHK(e, hipMemcpyAsync(reset_at_ns + off, e->d_reset, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
+        if (tokens) HIPCHK(e, hipMemcpyAsync(tokens + off, e->d_tok, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
+        HIPCHK(e, hipStreamSynchronize(s));
+    }
+    return RL_OK;
+}
+
+extern "C" int rl_peek_grid_cap(void) { return PEEK_GRID * PEEK_BLOCK; }
 
 extern "C" int rl_table_info_get(rl_engine* e, int64_t now_ms, rl_table_info* out) {
     if (!e || !out || out->struct_size < 8) return RL_EINVAL;

@@ -2,6 +2,7 @@
 #include "coalescer.hpp"
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <stdlib.h>
@@ -107,7 +108,12 @@ public:
         M_ = M;
         return RL_OK;
     }
-    int launch(int i, Slot& s) override {
+    int launch(int i, Slot& s) override { return launch_on(i, s, rl_decide_batch_device); }
+    int launch_peek(int i, Slot& s) override { return launch_on(i, s, rl_peek_batch_device); }
+    // rl_decide_batch_device / rl_peek_batch_device: one argument list
+    using DeviceFn = int (*)(rl_engine*, size_t, const uint64_t*, const int64_t*, const int64_t*, const uint32_t*,
+                             const int64_t*, uint8_t*, int64_t*, int64_t*, int64_t*, double*, void*);
+    int launch_on(int i, Slot& s, DeviceFn fn) {
         (void)hipSetDevice(dev_id_);   // the submitter thread
         Dev& d = dev_[i];
         Slot dv;
@@ -120,8 +126,7 @@ public:
             // stalls were the submitter blocked ~8 ms inside those calls
             // with the device idle (profiles/r3d_stall_trace.json)
             s.t_h2d = steady_ns();
-            int rc = rl_decide_batch_device(e_, m, s.key, s.ts, s.n, s.cfg, nullptr, s.dec, s.rem, s.retry, s.reset,
-                                            nullptr, os_);
+            int rc = fn(e_, m, s.key, s.ts, s.n, s.cfg, nullptr, s.dec, s.rem, s.retry, s.reset, nullptr, os_);
             if (rc != RL_OK) return rc;
             return hipEventRecord(d.ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
         }
@@ -133,8 +138,7 @@ public:
         ok &= await_event(d.ev_in) == hipSuccess;
         if (!ok) return RL_EDEVICE;
         s.t_h2d = steady_ns();
-        int rc = rl_decide_batch_device(e_, m, dv.key, dv.ts, dv.n, dv.cfg, nullptr, dv.dec, dv.rem, dv.retry,
-                                        dv.reset, nullptr, os_);
+        int rc = fn(e_, m, dv.key, dv.ts, dv.n, dv.cfg, nullptr, dv.dec, dv.rem, dv.retry, dv.reset, nullptr, os_);
         if (rc != RL_OK) return rc;
         ok = hipMemcpyAsync(s.dec, dv.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
         ok &= hipMemcpyAsync(s.rem, dv.rem, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
@@ -246,6 +250,10 @@ public:
         s.t_h2d = steady_ns();
         return b_.reset ? b_.reset(b_.user, cfg, key, ts) : RL_EINVAL;
     }
+    int launch_peek(int, Slot& s) override {
+        s.t_h2d = steady_ns();
+        return b_.peek ? b_.peek(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset) : RL_EINVAL;
+    }
     int wait(int, Slot&) override { return RL_OK; }
     int table_info(int64_t now_ms, rl_table_info* out) override {
         return b_.table_info ? b_.table_info(b_.user, now_ms, out) : RL_EINVAL;
@@ -324,9 +332,10 @@ void Coalescer::SetNotify(NotifyFn fn, void* user) {
 }
 
 int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
-                      uint64_t* ticket, int64_t deadline, void* tag) {
-    if (!ticket || (m && (!key || !ts || !n || !cfg)) || deadline < 0) return RL_EINVAL;
+                      uint64_t* ticket, int64_t deadline, void* tag, Op op) {
+    if (!ticket || (m && (!key || !ts || !n || !cfg)) || deadline < 0 || !has_requests(op)) return RL_EINVAL;
     Sub* s = get_sub(m);
+    s->op = op;
     s->deadline = deadline;
     s->tag = tag;
     if (trace_cap_) s->submit_ns = steady_ns();
@@ -345,7 +354,7 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
         // an empty submission is done at once; its ticket must still be unique
         next_seq_ += m ? m : 1;
         subs_[s->first] = s;
-        st_.submitted += m;
+        if (op == OP_REQ) st_.submitted += m;
         if (m) {
             queue_.push_back(s);
             s->in_queue = true;
@@ -495,7 +504,7 @@ int Coalescer::Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* 
     // done and applied: no slot or queue references it any more
     lk.unlock();
     const size_t m = s->m;
-    if (s->op == OP_REQ) {
+    if (has_requests(s->op)) {
         if (dec) memcpy(dec, s->dec, m);
         if (rem) memcpy(rem, s->rem, 8 * m);
         if (retry) memcpy(retry, s->retry, 8 * m);
@@ -706,6 +715,7 @@ void Coalescer::submitter() {
         Slot& s = slots_[si];
         s.parts.clear();
         s.is_reset = false;
+        s.is_peek = f->op == OP_PEEK;
         size_t m = 0;
         if (f->op == OP_RESET) {
             // like a one-request batch: enqueued between the batches around it
@@ -726,7 +736,8 @@ void Coalescer::submitter() {
                     maybe_free_locked(sub);
                     continue;
                 }
-                if (sub->op != OP_REQ) break;
+                // requests merge; a peek submission is launched on its own
+                if (sub->op != f->op || (s.is_peek && sub != f)) break;
                 if (sub->taken < sub->m && (sub->cancelled || (sub->deadline && sub->deadline <= now))) {
                     // its context ended before (the rest of) it was sent: that part is never applied
                     if (sub->taken == 0) drop_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
@@ -769,13 +780,20 @@ void Coalescer::submitter() {
                 memcpy(s.cfg + p.at, p.sub->cfg + p.off, 4 * p.count);
             }
             s.m = m;
-            auto_gc(s);
-            s.status = be_->launch(si, s);
+            if (s.is_peek) {
+                // inserts nothing: no part in the automatic GC's budgets
+                s.status = be_->launch_peek(si, s);
+            } else {
+                auto_gc(s);
+                s.status = be_->launch(si, s);
+            }
         }
         if (trace_cap_) s.t_launched = steady_ns();
         lk.lock();
-        st_.batches++;
-        st_.max_batch_seen = std::max<uint64_t>(st_.max_batch_seen, m);
+        if (!s.is_peek) {
+            st_.batches++;
+            st_.max_batch_seen = std::max<uint64_t>(st_.max_batch_seen, m);
+        }
         launched_.push_back(si);
         lk.unlock();
         cv_done_.notify_one();
@@ -826,7 +844,8 @@ void Coalescer::completer() {
                 else trace_[done_batches_ % trace_cap_] = t;
             }
             done_batches_++;
-            st_.decided += s.is_reset ? 1 : s.m;
+            if (s.is_peek) st_.peeked += s.m;
+            else st_.decided += s.is_reset ? 1 : s.m;
             for (const auto& p : s.parts) {
                 Sub* sub = p.sub;
                 if (st != RL_OK && !sub->truncated) sub->status = st;
@@ -882,8 +901,15 @@ extern "C" int rl_coalescer_create(rl_engine* e, const rl_coalescer_opts* opts, 
 
 extern "C" int rl_coalescer_create_with_host_backend(const rl_coalescer_backend* be, const rl_coalescer_opts* opts,
                                                      rl_coalescer** out) {
-    if (!be || be->struct_size != sizeof(rl_coalescer_backend) || !be->batch || !out) return RL_EINVAL;
-    return create(rlc::make_fn_backend(*be), opts, out);
+    // a caller compiled before `peek` was added passes the shorter struct
+    if (!be || !out ||
+        (be->struct_size != sizeof(rl_coalescer_backend) && be->struct_size != offsetof(rl_coalescer_backend, peek)))
+        return RL_EINVAL;
+    rl_coalescer_backend b{};
+    memcpy(&b, be, be->struct_size);
+    b.struct_size = sizeof b;
+    if (!b.batch) return RL_EINVAL;
+    return create(rlc::make_fn_backend(b), opts, out);
 }
 
 extern "C" int rl_coalescer_create_with_backend(rl_batch_fn fn, void* user, const rl_coalescer_opts* opts,
@@ -893,7 +919,7 @@ extern "C" int rl_coalescer_create_with_backend(rl_batch_fn fn, void* user, cons
 
 extern "C" int rl_coalescer_create_with_backends(rl_batch_fn fn, rl_reset_fn reset_fn, void* user,
                                                  const rl_coalescer_opts* opts, rl_coalescer** out) {
-    rl_coalescer_backend b{sizeof(rl_coalescer_backend), fn, reset_fn, nullptr, nullptr, user};
+    rl_coalescer_backend b{sizeof(rl_coalescer_backend), fn, reset_fn, nullptr, nullptr, user, nullptr};
     return rl_coalescer_create_with_host_backend(&b, opts, out);
 }
 
@@ -953,6 +979,16 @@ extern "C" int rl_coalescer_reset(rl_coalescer* c, uint64_t key_id, int64_t ts_n
     int rc = c->c->SubmitOp(rlc::OP_RESET, key_id, ts_ns, cfg_id, 0, 0, 0, &t);
     if (rc != RL_OK) return rc;
     return c->c->Wait(t, -1, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rl_coalescer_peek(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                 const int64_t* n, const uint32_t* cfg_id, uint8_t* decision, int64_t* remaining,
+                                 int64_t* retry_after_ns, int64_t* reset_at_ns) {
+    if (!c) return RL_EINVAL;
+    uint64_t t;
+    int rc = c->c->Submit(m, key_id, ts_ns, n, cfg_id, &t, 0, nullptr, rlc::OP_PEEK);
+    if (rc != RL_OK) return rc;
+    return c->c->Wait(t, -1, decision, remaining, retry_after_ns, reset_at_ns);
 }
 
 static int table_op(rl_coalescer* c, rlc::Op op, int64_t now_ms, uint64_t tb, uint64_t win, rl_table_info* out,

@@ -37,6 +37,7 @@ struct Slot {
     int64_t* reset = nullptr;
     size_t m = 0;
     bool is_reset = false;   // a Reset (parts[0].sub), not requests
+    bool is_peek = false;    // read-only queries (one OP_PEEK submission, or a part of it)
     int status = RL_OK;
     int64_t t_form = 0, t_h2d = 0, t_launched = 0;   // steady ns (batch trace)
     struct Part {
@@ -55,6 +56,9 @@ public:
     // Reset after every launched batch and before every later one,
     // asynchronous like a launch (completes through wait(slot))
     virtual int launch_reset(int slot, Slot& s, uint32_t cfg, uint64_t key, int64_t ts) = 0;
+    // read-only queries (rl_peek_batch_device) on the slot's staging arrays,
+    // ordered and completed like a launch
+    virtual int launch_peek(int slot, Slot& s) = 0;
     virtual int wait(int slot, Slot& s) = 0;     // until launch `slot` completed
     // synchronous table operations (the GPU engine drains its batches first)
     virtual int table_info(int64_t now_ms, rl_table_info* out) = 0;
@@ -78,7 +82,9 @@ public:
 std::unique_ptr<Backend> make_gpu_backend(rl_engine* e);
 std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b);
 
-enum Op : uint8_t { OP_REQ, OP_RESET, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE };
+enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE };
+// submissions that carry requests and results (the rest carry one operation)
+inline bool has_requests(Op op) { return op == OP_REQ || op == OP_PEEK; }
 // the synchronous table operations (run_table_op)
 inline bool is_table_op(Op op) { return op >= OP_INFO; }
 
@@ -143,8 +149,11 @@ public:
     ~Coalescer();
     int start();
     // tag: with SetNotify, the completion callback receives it
+    // op: OP_REQ, or OP_PEEK -- read-only queries, queued in sequence order
+    // like a Reset and launched on their own (not merged with requests or
+    // with other peeks); not counted in submitted / decided
     int Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
-               uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr);
+               uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr, Op op = OP_REQ);
     // a Reset / table count / table GC / snapshot / restore, queued in sequence order
     int SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
                  uint64_t cap_win, uint64_t* ticket, void* tag = nullptr, const SnapArgs* snap = nullptr);

@@ -37,6 +37,10 @@ public:
     Error Reset(const Context& ctx, const std::string& key) override;
     Error ResetAt(const Context& ctx, const std::string& key, int64_t t) override;
     Error Close() override { return inner_->Close(); }
+    // a peek is no decision: forwarded, not counted
+    Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) override {
+        return inner_->PeekN(ctx, key, n, now_ns, out);
+    }
     void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                     std::vector<BatchOutcome>* out) override;
     const Config& config() const override { return inner_->config(); }
@@ -73,6 +77,10 @@ public:
     Error Reset(const Context& ctx, const std::string& key) override;
     Error ResetAt(const Context& ctx, const std::string& key, int64_t t) override;
     Error Close() override { return inner_->Close(); }
+    // a peek is no decision: forwarded, not logged
+    Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) override {
+        return inner_->PeekN(ctx, key, n, now_ns, out);
+    }
     void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                     std::vector<BatchOutcome>* out) override;
     const Config& config() const override { return inner_->config(); }

@@ -211,7 +211,7 @@ struct Limiter {
 struct Io;
 struct Conn;
 
-enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET };
+enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK };   // K_PEEK: a read-only AllowN (rl_coalescer_peek)
 
 struct Stream {
     int32_t id = 0;
@@ -424,7 +424,7 @@ void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, c
         else respond_ok(c, st, msg);
         return;
     }
-    if (rpc.kind == K_ALLOW) {
+    if (rpc.kind == K_ALLOW || rpc.kind == K_PEEK) {
         const Outcome o = decide_outcome(rpc.lim, rpc.t, rc, dec ? dec[0] : 0, rem ? rem[0] : 0, retry ? retry[0] : 0,
                                          reset ? reset[0] : 0);
         if (o.code != GRPC_OK) return respond_err(c, st, o.code, o.r.error);
@@ -475,8 +475,8 @@ void submit_rpc(Io* io, Conn* c, Stream* st, Rpc&& rpc, size_t m, const uint64_t
     uint64_t ticket = 0;
     int rc;
     if (rpc.kind == K_RESET) rc = s->co->SubmitOp(rlc::OP_RESET, key[0], ts[0], cfg[0], 0, 0, 0, &ticket, io);
-    else rc = s->co->Submit(m, key, ts, n, cfg, &ticket, rpc.deadline, io);
-    s->n_dec += m;
+    else rc = s->co->Submit(m, key, ts, n, cfg, &ticket, rpc.deadline, io, rpc.kind == K_PEEK ? rlc::OP_PEEK : rlc::OP_REQ);
+    if (rpc.kind != K_PEEK) s->n_dec += m;   // a peek decides nothing
     if (rc != RL_OK) {   // queue full / closed: the error branch at once
         finish_rpc(io, 0, rpc, rc, nullptr, nullptr, nullptr, nullptr);
         return;
@@ -506,19 +506,24 @@ void dispatch(Conn* c, Stream* st) {
         put_int(out, 1, status);
         return respond_ok(c, st, out);
     }
-    if (p.compare(0, svc.size(), svc) != 0) return respond_err(c, st, GRPC_UNIMPLEMENTED, "unknown service");
-    const std::string m = p.substr(svc.size());
-    if (m == "Allow" || m == "AllowN" || m == "Reset") {
+    static const std::string peek_path = "/ratelimiter.v1.RateLimiterStatus/Peek";
+    const bool is_peek = p == peek_path;
+    if (!is_peek && p.compare(0, svc.size(), svc) != 0) return respond_err(c, st, GRPC_UNIMPLEMENTED, "unknown service");
+    const std::string m = is_peek ? "RateLimiterStatus/Peek" : p.substr(svc.size());
+    if (m == "Allow" || m == "AllowN" || m == "Reset" || is_peek) {
         ReqMsg r;
         if (!parse_req(msg, &r)) return respond_err(c, st, GRPC_INTERNAL, "bad request message");
         const Limiter* lim = s->find(r.limiter);
         if (!lim) return respond_err(c, st, GRPC_NOT_FOUND, "unknown limiter " + py_repr(r.limiter));
         if (m == "Allow") r.n = 1;
         if (m == "AllowN" && r.n <= 0) return respond_err(c, st, GRPC_INVALID_ARGUMENT, ERR_INVALID_N);
+        // Peek: an omitted n (proto3 zero) is the status query; queued, expired and
+        // cancelled like an Allow -- one dropped before its launch was never run
+        if (is_peek && r.n < 0) return respond_err(c, st, GRPC_INVALID_ARGUMENT, ERR_INVALID_N);
         const int64_t t = s->now();
         const uint64_t id = s->key_id(lim, r.key);
         const size_t mm = m == "Reset" ? 0 : 1;
-        Rpc rpc{c, st->id, m == "Reset" ? K_RESET : K_ALLOW, t, 0, lim, {}, mm};
+        Rpc rpc{c, st->id, m == "Reset" ? K_RESET : is_peek ? K_PEEK : K_ALLOW, t, 0, lim, {}, mm};
         const int64_t n = r.n;
         const uint32_t cfg = lim->cfg;
         return submit_rpc(io, c, st, std::move(rpc), mm, &id, &t, &n, &cfg);

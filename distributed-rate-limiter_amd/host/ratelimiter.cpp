@@ -167,6 +167,14 @@ uint64_t Engine::Intern(const std::string& formatted_key) {
     return id;
 }
 
+bool Engine::Lookup(const std::string& formatted_key, uint64_t* id) {
+    std::lock_guard<std::mutex> g(intern_mu_);
+    auto it = ids_.find(formatted_key);
+    if (it == ids_.end()) return false;
+    *id = it->second;
+    return true;
+}
+
 std::string Engine::Name(uint64_t id) {
     std::lock_guard<std::mutex> g(intern_mu_);
     return id < names_.size() ? names_[id] : std::string();
@@ -278,6 +286,49 @@ public:
                 o.err = Error::New(Error::Other, "failed to check rate limit: " + why);
             }
         }
+    }
+
+    // AllowN's error mapping around rl_peek_batch; n == 0 is accepted
+    Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) override {
+        if (n < 0) return ErrInvalidN;
+        const int64_t t = now_ns == INT64_MIN ? eng_->clock() : now_ns;
+        // a name the interner has never seen stays unseen: any id without
+        // state gives its answer (interned ids count up from 0, and this one
+        // is not the reserved id either)
+        uint64_t id = UINT64_MAX - 1;
+        (void)eng_->Lookup(cfg_.FormatKey(key), &id);
+        const int64_t sms = eng_->server_ms_override != INT64_MIN ? eng_->server_ms_override
+                                                                  : rl::floor_div(t, 1000000LL);
+        uint8_t dec = rl::DEC_INVALID;
+        int64_t rem = 0, retry = 0, reset = 0;
+        std::string cause;
+        int rc = RL_OK;
+        if (closed_.load()) {
+            cause = "engine: client is closed";
+            rc = RL_EINVAL;
+        } else if (ctx.cancelled.load()) {
+            cause = "context canceled";
+            rc = RL_EINVAL;
+        } else if (ctx.deadline_ns && eng_->clock() >= ctx.deadline_ns) {
+            cause = "context deadline exceeded";
+            rc = RL_EINVAL;
+        } else {
+            std::lock_guard<std::mutex> g(eng_->mu());
+            rc = rl_peek_batch(eng_->raw(), 1, &id, &t, &n, &cfg_id_, &sms, &dec, &rem, &retry, &reset, nullptr);
+            if (rc != RL_OK) cause = engine_error(eng_->raw(), rc);
+        }
+        if (rc == RL_OK && (dec == rl::DEC_ALLOWED || dec == rl::DEC_DENIED)) {
+            if (out) *out = Result{dec == rl::DEC_ALLOWED, cfg_.Limit, rem, retry, reset};
+            return Error{};
+        }
+        if (cfg_.FailOpen) {
+            if (out) *out = Result{true, cfg_.Limit, 0, 0, fail_open_reset_at(t)};
+            return Error{};
+        }
+        const std::string why = rc != RL_OK ? cause
+                                : dec == rl::DEC_ERROR ? "ERR increment or decrement would overflow"
+                                                       : "engine rejected the request";
+        return Error::New(Error::Other, "failed to check rate limit: " + why);
     }
 
     Error Reset(const Context& ctx, const std::string& key) override {
@@ -607,6 +658,18 @@ extern "C" int rll_allow_n(rll_limiter* l, const char* key, size_t keylen, int64
     if (outs[0].has_result && out) to_c(outs[0].result, out);
     if (outs[0].err) put_err(err, errlen, outs[0].err.msg);
     return code_of(outs[0].err);
+}
+
+extern "C" int rll_peek_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int64_t now_ns,
+                          int ctx_cancelled, rll_result* out, char* err, size_t errlen) {
+    if (!l || (!key && keylen)) return RLL_ERR_ARG;
+    Context ctx;
+    ctx.cancelled.store(ctx_cancelled != 0);
+    Result r;
+    const Error e = l->lim->PeekN(ctx, std::string(key ? key : "", keylen), n, now_ns, &r);
+    if (!e && out) to_c(r, out);
+    if (e) put_err(err, errlen, e.msg);
+    return code_of(e);
 }
 
 extern "C" int rll_allow_batch(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens,

@@ -110,6 +110,8 @@ public:
     ~Engine();
     rl_engine* raw() { return e_; }
     uint64_t Intern(const std::string& formatted_key);
+    // lookup only: false (and nothing interned) for a name never seen
+    bool Lookup(const std::string& formatted_key, uint64_t* id);
     // the formatted key of an interned id ("" if unknown)
     std::string Name(uint64_t id);
     std::mutex& mu() { return mu_; }
@@ -145,6 +147,10 @@ public:
     // Reset as if called at Unix time t (deterministic replay)
     virtual Error ResetAt(const Context& ctx, const std::string& key, int64_t t) = 0;
     virtual Error Close() = 0;
+    // Peek (new; rl_peek_batch): the Result AllowN(key, n) would return at
+    // now_ns (INT64_MIN: the engine clock), changing nothing.  n == 0 asks how
+    // much is left; n < 0 is ErrInvalidN.  A key never seen is not interned.
+    virtual Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) = 0;
     // request-coalescing path (new): one engine launch for many requests
     virtual void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                             std::vector<BatchOutcome>* out) = 0;

@@ -116,7 +116,7 @@ class rl_coalescer_opts(_Sized):
 class rl_coalescer_stats(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("pad_", C.c_uint32)] + [
         (k, C.c_uint64) for k in ("submitted", "decided", "batches", "max_batch_seen", "pending", "expired",
-                                  "cancelled", "gc_runs", "gc_checks", "gc_failures")]
+                                  "cancelled", "gc_runs", "gc_checks", "gc_failures", "peeked")]
 
 
 vp = C.c_void_p
@@ -129,7 +129,7 @@ GC_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(rl
 
 class rl_coalescer_backend(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("batch", BATCH_FN), ("reset", RESET_FN), ("table_info", INFO_FN),
-                ("gc", GC_FN), ("user", vp)]
+                ("gc", GC_FN), ("user", vp), ("peek", BATCH_FN)]
 
 _sig = {
     "rl_engine_create": (C.c_int, [C.POINTER(rl_opts), C.POINTER(vp)]),
@@ -137,6 +137,12 @@ _sig = {
     "rl_config_register": (C.c_int, [vp, C.c_uint8, C.c_int64, C.c_int64, C.POINTER(C.c_uint32)]),
     "rl_decide_batch": (C.c_int, [vp, C.c_size_t] + [vp] * 10),
     "rl_decide_batch_device": (C.c_int, [vp, C.c_size_t] + [vp] * 11),
+    "rl_peek_batch": (C.c_int, [vp, C.c_size_t] + [vp] * 10),
+    "rl_peek_batch_device": (C.c_int, [vp, C.c_size_t] + [vp] * 11),
+    "rl_peek_grid_cap": (C.c_int, []),
+    "rl_coalescer_peek": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
+    "rll_peek_n": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int,
+                             C.POINTER(rll_result), C.c_char_p, C.c_size_t]),
     "rl_engine_sync": (C.c_int, [vp]),
     "rl_reset": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int64]),
     "rl_reset_device": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int64, vp]),
@@ -256,6 +262,8 @@ class Decisions:
 
 # rl_opts.flags (include/rl_engine.h)
 OPT_PIPELINE = 1
+# requests one k_peek launch covers at one request per thread (grid cap x block size)
+PEEK_GRID_CAP = lib.rl_peek_grid_cap()
 
 
 class Engine:
@@ -336,6 +344,31 @@ class Engine:
                       stream=None):
         rc = lib.rl_decide_batch_device(self.h, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, rem_p,
                                         retry_p, reset_p, tok_p, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def peek(self, key, ts, n, cfg, server_ms=None, want_tokens=True) -> Decisions:
+        """rl_peek_batch: what decide() would return for each request, with
+        nothing changed; n == 0 asks how much is left"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        sms = None if server_ms is None else np.ascontiguousarray(server_ms, dtype=np.int64)
+        m = key.size
+        out = Decisions(np.empty(m, np.uint8), np.empty(m, np.int64), np.empty(m, np.int64),
+                        np.empty(m, np.int64), np.empty(m, np.float64) if want_tokens else None)
+        rc = lib.rl_peek_batch(self.h, m, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), _ptr(sms),
+                               _ptr(out.decision), _ptr(out.remaining), _ptr(out.retry_after_ns),
+                               _ptr(out.reset_at_ns), _ptr(out.tokens))
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        return out
+
+    def peek_device(self, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, rem_p, retry_p, reset_p, tok_p,
+                    stream=None):
+        rc = lib.rl_peek_batch_device(self.h, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, rem_p,
+                                      retry_p, reset_p, tok_p, stream)
         if rc != RL_OK:
             raise EngineError(rc, self.last_error())
 
@@ -654,6 +687,17 @@ class RateLimiter:
             return Result(bool(r.allowed), r.limit, r.remaining, r.retry_after_ns, r.reset_at_ns), None, rc
         return None, buf.value.decode(), rc
 
+    def peek_n(self, key, n=0, now_ns=NOW_WALL, cancelled=False):
+        """rll_peek_n: (Result | None, error message | None, code); n == 0 asks
+        how much is left, nothing changes"""
+        r = rll_result()
+        buf = C.create_string_buffer(512)
+        kb = key.encode()
+        rc = lib.rll_peek_n(self.h, kb, len(kb), n, now_ns, 1 if cancelled else 0, C.byref(r), buf, 512)
+        if rc == RLL_OK:
+            return Result(bool(r.allowed), r.limit, r.remaining, r.retry_after_ns, r.reset_at_ns), None, rc
+        return None, buf.value.decode(), rc
+
     def batch_allow(self, keys, n, now_ns=None):
         m = len(keys)
         kbs = [k.encode() for k in keys]
@@ -747,7 +791,7 @@ class Coalescer:
     gc_interval_ns > 0 turns on the automatic table GC (rl_coalescer_opts)."""
 
     def __init__(self, engine, max_batch=65536, max_in_flight=3, linger_ns=0, queue_cap=0, reset=None,
-                 table_info=None, gc=None, gc_interval_ns=0, gc_high_pct=0, gc_margin_ms=0,
+                 table_info=None, gc=None, peek=None, gc_interval_ns=0, gc_high_pct=0, gc_margin_ms=0,
                  gc_max_tb_capacity=0, gc_max_win_capacity=0):
         o = rl_coalescer_opts(max_batch=max_batch, max_in_flight=max_in_flight, gc_high_pct=gc_high_pct,
                               linger_ns=linger_ns, queue_cap=queue_cap, gc_interval_ns=gc_interval_ns,
@@ -762,7 +806,8 @@ class Coalescer:
             self._be = rl_coalescer_backend(
                 batch=BATCH_FN(engine), reset=RESET_FN(reset) if reset else C.cast(None, RESET_FN),
                 table_info=INFO_FN(table_info) if table_info else C.cast(None, INFO_FN),
-                gc=GC_FN(gc) if gc else C.cast(None, GC_FN), user=None)
+                gc=GC_FN(gc) if gc else C.cast(None, GC_FN), user=None,
+                peek=BATCH_FN(peek) if peek else C.cast(None, BATCH_FN))
             rc = lib.rl_coalescer_create_with_host_backend(C.byref(self._be), C.byref(o), C.byref(h))
         if rc != RL_OK:
             raise EngineError(rc, "rl_coalescer_create failed")
@@ -797,6 +842,18 @@ class Coalescer:
 
     def reset(self, key, ts, cfg) -> int:
         return lib.rl_coalescer_reset(self.h, key, ts, cfg)
+
+    def peek(self, key, ts, n, cfg):
+        """rl_coalescer_peek: read-only queries in sequence order; blocks.
+        -> (rc, (decision, remaining, retry_after_ns, reset_at_ns))"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        m = key.size
+        out = (np.empty(m, np.uint8), np.empty(m, np.int64), np.empty(m, np.int64), np.empty(m, np.int64))
+        rc = lib.rl_coalescer_peek(self.h, m, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), *[_ptr(x) for x in out])
+        return rc, out
 
     def table_info(self, now_ms):
         out = rl_table_info()

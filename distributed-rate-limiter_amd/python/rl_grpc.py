@@ -194,5 +194,16 @@ def rate_limiter_stub(channel):
     return Stub(channel, api("ratelimiter.proto"), "RateLimiter")
 
 
+def status_stub(channel):
+    """the read-only service (RateLimiterStatus: Peek)"""
+    return Stub(channel, api("ratelimiter.proto"), "RateLimiterStatus")
+
+
+def peek(stub, limiter: str, key: str, n: int = 0, **kw):
+    """RateLimiterStatus.Peek (stub: status_stub(channel)): the AllowResponse AllowN(key, n) would get now, with
+    nothing consumed; n = 0 (the default) asks how much is left"""
+    return stub.Peek(api("ratelimiter.proto").AllowNRequest(limiter=limiter, key=key, n=n), **kw)
+
+
 def health_stub(channel):
     return Stub(channel, api("health.proto"), "Health")

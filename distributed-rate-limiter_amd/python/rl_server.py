@@ -200,6 +200,20 @@ class RateLimiterService:
     def AllowN(self, req, ctx):
         return self._allow_n(req.limiter, req.key, req.n, ctx)
 
+    def Peek(self, req, ctx):
+        """the AllowResponse AllowN(key, n) would get now, with nothing changed
+        (rl_coalescer_peek); an omitted n (0) asks how much is left.  Blocks
+        like Reset: queued in sequence order, no deadline of its own."""
+        lim = self._limiter(req.limiter, ctx)
+        if req.n < 0:
+            ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, ERR_INVALID_N)
+        t = self.clock()
+        rc, (dec, rem, retry, reset) = self.co.peek([self._key_id(lim, req.key)], [t], [req.n], [lim.cfg_id])
+        res, err, code = self._result(lim, t, rc, int(dec[0]), int(rem[0]), int(retry[0]), int(reset[0]))
+        if err:
+            ctx.abort(code, err)
+        return res
+
     def Reset(self, req, ctx):
         lim = self._limiter(req.limiter, ctx)
         rc = self.co.reset(self._key_id(lim, req.key), self.clock(), lim.cfg_id)
@@ -251,7 +265,8 @@ class RateLimiterService:
 def build_server(service: RateLimiterService, address: str, workers: int = 64) -> tuple[grpc.Server, int]:
     server = grpc.server(futures.ThreadPoolExecutor(max_workers=workers),
                          options=[("grpc.so_reuseport", 0)])
-    for a, sname, impl in ((service.a, "RateLimiter", service), (service.h, "Health", service)):
+    for a, sname, impl in ((service.a, "RateLimiter", service), (service.a, "RateLimiterStatus", service),
+                           (service.h, "Health", service)):
         handlers = {}
         for mname, inp, out in a.services[sname]:
             handlers[mname] = grpc.unary_unary_rpc_method_handler(

@@ -104,6 +104,7 @@ typedef struct rl_coalescer_stats {
     uint64_t gc_runs;        /* table GCs (automatic and rl_coalescer_gc) */
     uint64_t gc_checks;      /* automatic occupancy counts */
     uint64_t gc_failures;    /* GCs that returned an error (the old tables stay) */
+    uint64_t peeked;         /* read-only queries completed (rl_coalescer_peek); not in submitted / decided */
 } rl_coalescer_stats;
 
 /* Signature of rl_decide_batch (host arrays, synchronous).  A backend of this
@@ -128,6 +129,8 @@ typedef struct rl_coalescer_backend {
     rl_info_fn table_info;
     rl_gc_fn gc;
     void* user;
+    rl_batch_fn peek;        /* rl_peek_batch: must leave the backend's state unchanged (a caller compiled
+                                before this field passes the shorter struct_size: no peek) */
 } rl_coalescer_backend;
 
 /* Coalescer over a GPU engine, on the device current on the calling thread
@@ -184,6 +187,17 @@ int rl_coalescer_decide_deadline(rl_coalescer* c, uint64_t key_id, int64_t ts_ns
  * request submitted after it.  Blocks until applied.  The DEL is enqueued on
  * the engine's replay stream like a batch: the pipeline is not drained. */
 int rl_coalescer_reset(rl_coalescer* c, uint64_t key_id, int64_t ts_ns, uint32_t cfg_id);
+/* Read-only queries (rl_peek_batch_device, include/rl_engine.h): for each
+ * request the Result AllowN would return, against the state left by every
+ * request submitted before the call and none submitted after it; nothing is
+ * changed, n == 0 asks how much is left.  Queued in sequence order like Reset,
+ * on the engine's replay stream: the pipeline is not drained.  Blocks until
+ * done.  Not counted in submitted / decided (stats.peeked) nor in the
+ * automatic GC's insert budgets.  RL_EINVAL over a host backend without
+ * `peek`. */
+int rl_coalescer_peek(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                      const int64_t* n, const uint32_t* cfg_id, uint8_t* decision, int64_t* remaining,
+                      int64_t* retry_after_ns, int64_t* reset_at_ns);
 /* rl_table_info_get / rl_table_gc in sequence order (both drain the
  * engine's in-flight batches first).  Block until done. */
 int rl_coalescer_table_info(rl_coalescer* c, int64_t now_ms, rl_table_info* out);

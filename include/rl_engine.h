@@ -155,6 +155,37 @@ int rl_reset(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns);
  * stream) waits for it. */
 int rl_reset_device(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns, void* stream);
 
+/* Peek: read-only quota queries.  For each request, the outputs
+ * rl_decide_batch would give for it at (ts_ns, server_ms) against the state
+ * left by every batch enqueued before the call -- and nothing changes: no key
+ * is inserted, no tokens stored, no INCRBY, no TTL refresh, no lazy-expiry
+ * deletion, no spill slot claimed; rl_stats.batches / .decisions and the
+ * sticky status of rl_engine_sync are untouched.  Requests of one call do not
+ * see each other.  n == 0 is legal here only, the status query: a token bucket
+ * answers RL_ALLOWED with remaining = floor(tokens after refill) (unless ts_ns
+ * lies so far before its last refill that the refill leaves tokens < 0), a window
+ * limiter with remaining = max(limit - count, 0).  n < 0, an unknown cfg_id and
+ * RL_KEY_RESERVED yield RL_INVALID; a window count whose INCRBY would overflow
+ * RL_ERROR with reset_at_ns, as in rl_decide_batch.  A key without state (never
+ * seen, expired, or in a table too full to take it) answers as a fresh key.
+ * m may exceed max_batch. */
+int rl_peek_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                  const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                  uint8_t* decision, int64_t* remaining, int64_t* retry_after_ns,
+                  int64_t* reset_at_ns, double* tokens);
+/* Same, with device pointers, ordered as rl_reset_device: after every batch
+ * enqueued before the call, before every batch enqueued after it (one kernel
+ * on the engine's replay stream, nothing is drained); `stream` (a hipStream_t,
+ * NULL = the engine's stream) waits for the results.  Without RL_OPT_PIPELINE
+ * the kernel first waits for the work queued on `stream` (the inputs). */
+int rl_peek_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                         const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                         uint8_t* decision, int64_t* remaining, int64_t* retry_after_ns,
+                         int64_t* reset_at_ns, double* tokens, void* stream);
+/* requests one rl_peek_batch launch covers with one request per thread (grid
+ * cap x block size); a larger batch strides */
+int rl_peek_grid_cap(void);
+
 int rl_engine_stats(rl_engine* e, rl_stats* out);
 
 /* State-table occupancy.  A key is live at server clock now_ms when its Redis

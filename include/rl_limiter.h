@@ -85,6 +85,14 @@ int rll_new(rll_engine* e, const char* algorithm, int64_t limit, int64_t window_
 int rll_allow_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int64_t now_ns,
                 int ctx_cancelled, rll_result* out, char* err, size_t errlen);
 
+/* Peek: the Result AllowN(ctx, key, n) would return, with nothing changed
+ * (rl_peek_batch, include/rl_engine.h).  As rll_allow_n, except that n == 0 is
+ * accepted (how much is left) and only n < 0 is RLL_ERR_INVALID_N.  A key the
+ * interner has never seen is not interned; the metrics and logging decorators
+ * forward a peek unrecorded. */
+int rll_peek_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int64_t now_ns,
+               int ctx_cancelled, rll_result* out, char* err, size_t errlen);
+
 /* BatchAllow: m requests in one engine launch; per-request code in codes[] */
 int rll_allow_batch(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens,
                     const int64_t* n, const int64_t* now_ns, rll_result* out, int32_t* codes);
