@@ -612,6 +612,10 @@ struct rl_engine {
     // sorted-order scratch (reused by consecutive small batches, which the
     // chain stream orders)
     uint32_t small_max = 0;
+    // batches up to up_max finish through arrival-index buckets, larger ones
+    // through k_unpermute / k_unpermute_routed (RL_UP_MAX lowers it: the
+    // buckets and their counters are sized for UP_MAX)
+    uint32_t up_max = UP_MAX;
     int64_t *s_ts = nullptr, *s_n = nullptr, *s_sms = nullptr;
     uint32_t* s_cfg = nullptr;
     uint8_t* s_dec = nullptr;
@@ -872,6 +876,7 @@ extern "C" int rl_engine_create(const rl_opts* o, rl_engine** out) {
     if (hipEventCreateWithFlags(&e->ev_peek, hipEventDisableTiming) != hipSuccess) return bail(RL_EDEVICE);
     e->small_max = SMALL_MAX;
     if (const char* v = getenv("RL_SMALL_MAX")) e->small_max = std::min<uint32_t>((uint32_t)atoi(v), SMALL_MAX);
+    if (const char* v = getenv("RL_UP_MAX")) e->up_max = std::min<uint32_t>((uint32_t)std::max(0, atoi(v)), UP_MAX);
     size_t M = e->max_batch;
     e->cfg_cap = 64;
     const size_t status_words = (size_t)4 * e->max_tiles * RADIX;
@@ -1296,13 +1301,15 @@ static int run_batch(rl_engine* e, uint32_t m, ReqArgs a, hipStream_t s, bool in
         // a routed batch: one result record per request at its receive
         // index, through merge-position buckets (no scattered 32-byte stores:
         // routed mixed +3.5 %, profiles/r4w_ab_routed_finish.txt)
-        if (m <= UP_MAX) {
+        if (m <= e->up_max) {
             k_unpermute_bucket<<<(m + 256 * UP_ITEMS - 1) / (256 * UP_ITEMS), 256, GROUP_LDS, t>>>(
                 kin, vfin, m, e->invalid_key, ps, B.upb, B.ctrl + CTRL_UPB, ri->count);
             k_unpermute_routed_out<<<(m + UP_BUCKET - 1) / UP_BUCKET, 256, 0, t>>>(m, B.upb, e->d_cfg, *ri);
-        } else
+        } else {
             k_unpermute_routed<<<pgrid, 256, GROUP_LDS, t>>>(kin, vfin, m, e->invalid_key, e->d_cfg, ps, *ri);
-    } else if (m <= UP_MAX) {
+            e->stats.plain_finish_batches++;
+        }
+    } else if (m <= e->up_max) {
         // results to the caller's order through arrival-index buckets: no
         // scattered partial-line stores
         k_unpermute_bucket<<<(m + 256 * UP_ITEMS - 1) / (256 * UP_ITEMS), 256, GROUP_LDS, t>>>(
@@ -1310,6 +1317,7 @@ static int run_batch(rl_engine* e, uint32_t m, ReqArgs a, hipStream_t s, bool in
         k_unpermute_bucket_out<<<(m + UP_BUCKET - 1) / UP_BUCKET, 256, 0, t>>>(m, B.upb, e->d_cfg, a);
     } else {
         k_unpermute<<<pgrid, 256, GROUP_LDS, t>>>(kin, vfin, m, e->invalid_key, e->d_cfg, ps, a);
+        e->stats.plain_finish_batches++;
     }
     if (sr) k_stamp<<<1, 64, 0, t>>>(sr + 5);
     if (timed) {
@@ -1379,12 +1387,16 @@ static int warm_up(rl_engine* e) {
         e->force_light = false;
         if (r != RL_OK) return r;
     }
-    {   // the routed path's kernels (k_probe<.., true>, k_unpermute_routed) on a
-        // batch whose device size is 0: every kernel returns at once
+    {   // the routed path's kernels (k_probe<.., true>, k_unpermute_routed_out) on
+        // a batch whose device size is 0: every kernel returns at once
         ReqArgs ar{nullptr, nullptr, nullptr, nullptr, e->d_sms, nullptr, nullptr, nullptr, nullptr, nullptr};
         const RouteIn ri{nullptr, nullptr, e->d_zero, nullptr};
         const int r = run_batch(e, mb, ar, s, false, nullptr, &ri);
         if (r != RL_OK) return r;
+        // the finish of batches above up_max, which no warm-up batch reaches
+        // (mb <= up_max unless RL_UP_MAX says otherwise): zero-sized launches
+        k_unpermute_routed<<<1, 256, GROUP_LDS, s>>>(nullptr, nullptr, 0u, e->invalid_key, e->d_cfg, ar, ri);
+        k_unpermute<<<1, 256, GROUP_LDS, s>>>(nullptr, nullptr, 0u, e->invalid_key, e->d_cfg, a, a);
     }
     {   // the read-only query kernel
         const int r = run_peek(e, 1, a, s, false);

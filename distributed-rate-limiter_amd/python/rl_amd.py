@@ -73,6 +73,7 @@ class rl_stats(_Sized):
         ("coop_ends", C.c_uint64 * 4),
         ("sort_predicted", C.c_uint64),
         ("light_batches", C.c_uint64),
+        ("plain_finish_batches", C.c_uint64),
     ]
 
 

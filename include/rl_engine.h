@@ -103,6 +103,9 @@ typedef struct rl_stats {
     uint64_t sort_predicted;   /* batches whose grouping sort was launched as k_sort_local only (every
                                   MSD bucket predicted to fit LDS: no LSD passes, no k_segments) */
     uint64_t light_batches;    /* batches replayed by the light replay kernel (no huge segment expected) */
+    uint64_t plain_finish_batches; /* batches above the bucketed finish's limit (2^21 requests, or RL_UP_MAX
+                                      when lower): results scattered by arrival index (k_unpermute, or
+                                      k_unpermute_routed on the routed path) */
 } rl_stats;
 
 /* replaces redis.NewClient + NewTokenBucket/NewSlidingWindow/NewFixedWindow's

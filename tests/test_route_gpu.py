@@ -389,6 +389,7 @@ def _routed_rank(rank, world, port, backend, batches_of, q, exchange=None, cap=N
         info["router_status"] = router.sync(None)
         info["collectives"] = pipe.collectives
         info["exchange"] = pipe.exchange
+        info["plain_finish_batches"] = int(eng.stats().plain_finish_batches)   # steps through k_unpermute_routed
         exp = route_ops.shared_limiter_expectations(all_batches, rank, configs, profile=profile,
                                                     cap=router.capacity)
         ok = True

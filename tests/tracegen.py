@@ -89,6 +89,79 @@ def random_config_trace(seed, alg, m, nk=None):
     return configs, (key, ts, n, cfg, None)
 
 
+def many_configs(seed, N, tb_ids=None):
+    """N seeded configs cycling TB / SW / FW (config i: algorithm 1 + i % 3),
+    with pairwise distinct (limit, window): limits 2 .. 40 and windows 0.3 ..
+    12 s, so that allows, denials and expiries all occur in a trace whose gaps
+    average ~0.1 s.  The ids in tb_ids (default: N - 1, the last) are token
+    buckets whatever the cycle says, refilling 0.4 .. 4 tokens/s: a hot key on
+    one is allowed and denied in turns."""
+    rng = np.random.default_rng(seed)
+    tb_ids = (N - 1,) if tb_ids is None else tb_ids
+    out = []
+    for i in range(N):
+        L = int(rng.integers(2, 41))
+        W = int(rng.integers(300, 12_000)) * 1_000_000 + i * 1000     # + i us: distinct windows
+        if i in tb_ids:
+            out.append((1, int(rng.integers(5, 26)), int(rng.integers(6000, 12_000)) * 1_000_000 + i * 1000))
+        else:
+            out.append((1 + i % 3, L, W))
+    return out
+
+
+def many_config_keys(N, c, j):
+    """key j of config c: cfg = key % N"""
+    return np.uint64(c + N * (1000 + j))
+
+
+def many_config_trace(seed, N, nbatch=3, m=24_000, hot=4500, nlight=2500, tb_ids=None):
+    """`nbatch` batches of m requests over N configs (many_configs), cfg =
+    key % N: ~nlight light keys that use every config id up to N - 1; one hot
+    token-bucket key on config N - 1 with `hot` requests in every batch (a
+    huge segment: the chain); per batch one key of 600 and one of 40 requests
+    on each of the configs N - 1 (TB), N - 2, N - 3 and 0, 1, 2 (heavy
+    segments: one wave each); n up to 50, 2 % of 2^62 and 1 % of 0
+    (rejected).  -> (configs, (key, ts, n, cfg, None), [m] * nbatch)"""
+    rng = np.random.default_rng(seed)
+    configs = many_configs(seed, N, tb_ids)
+    heavy_cfgs = [N - 1, N - 2, N - 3, 0, 1, 2]
+    keys = []
+    for b in range(nbatch):
+        parts = [np.full(hot, many_config_keys(N, N - 1, 0))]
+        for c in heavy_cfgs:
+            parts.append(np.full(600, many_config_keys(N, c, 1)))
+            parts.append(np.full(40, many_config_keys(N, c, 2)))
+        used = sum(p.size for p in parts)
+        parts.append(rng.integers(0, nlight, m - used).astype(np.uint64))
+        k = np.concatenate(parts).astype(np.uint64)
+        keys.append(k[rng.permutation(m)])
+    key = np.concatenate(keys)
+    M = key.size
+    gaps = rng.choice([0, 1, 1000, 250_000, 50_000_000, 700_000_000, 3 * NS], M,
+                      p=[0.05, 0.05, 0.4, 0.2, 0.2, 0.08, 0.02])
+    ts = T0 + np.cumsum(gaps).astype(np.int64)
+    n = rng.choice([1, 1, 1, 2, 3, 7, 50], M).astype(np.int64)
+    n[rng.random(M) < 0.02] = 1 << 62
+    n[rng.random(M) < 0.01] = 0
+    cfg = (key % np.uint64(N)).astype(np.uint32)
+    return configs, (key, ts, n, cfg, None), [m] * nbatch
+
+
+def many_config_light_trace(seed, N, nbatch=2, m=1 << 19, nkeys=60_000):
+    """`nbatch` batches of m requests over N configs with no hot key (uniform
+    keys, cfg = key % N, ~9 requests per key and batch, ~30 us gaps: a key
+    comes back every ~2 s)"""
+    rng = np.random.default_rng(seed)
+    configs = many_configs(seed, N)
+    M = nbatch * m
+    key = rng.integers(0, nkeys, M).astype(np.uint64)
+    ts = T0 + np.cumsum(rng.choice([0, 1000, 20_000, 100_000], M)).astype(np.int64)
+    n = rng.choice([1, 1, 1, 2, 3, 7], M).astype(np.int64)
+    n[rng.random(M) < 0.005] = 1 << 62
+    cfg = (key % np.uint64(N)).astype(np.uint32)
+    return configs, (key, ts, n, cfg, None), [m] * nbatch
+
+
 DAY = 86400 * NS
 # windows Validate accepts past a day (config.go:41-46: 1 ms <= W <= 365 d):
 # one day; seven days (Truncate's year-1 offset is 259200 s, fixedwindow.go:72);
