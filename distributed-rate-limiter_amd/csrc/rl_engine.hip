@@ -28,6 +28,7 @@
 #include "../../include/rl_route.h"
 #include "../../include/rl_snapshot.h"
 #include "rl_peek.h"
+#include "rl_reset.h"
 #include "rl_replay.h"
 #include "rl_semantics.h"
 #include "rl_snapshot.h"
@@ -1358,6 +1359,27 @@ static int run_peek(rl_engine* e, size_t m, ReqArgs a, hipStream_t s, bool input
     return RL_OK;
 }
 
+// enqueue one batch of resets (rl_reset.h) of any size: k_reset_batch on
+// `chain`, where rl_reset_device puts its DEL -- after the replay of every
+// batch enqueued before, before that of every batch enqueued after; s waits
+// for it.  Nothing is counted in rl_stats and no error flag is raised.
+static int run_reset_batch(rl_engine* e, size_t m, const uint64_t* key, const int64_t* ts, const uint32_t* cfg,
+                           uint8_t* status, hipStream_t s, bool inputs_ready) {
+    if (m == 0) return RL_OK;
+    hipStream_t c = e->chain;
+    if (!inputs_ready) {
+        HIPCHK(e, hipEventRecord(e->ev_in, s));
+        HIPCHK(e, hipStreamWaitEvent(c, e->ev_in, 0));
+    }
+    const int grid = (int)std::min<size_t>((m + RESET_BLOCK - 1) / RESET_BLOCK, (size_t)RESET_GRID);
+    k_reset_batch<<<grid, RESET_BLOCK, 0, c>>>((uint64_t)m, key, ts, cfg, status, e->d_cfg, (uint32_t)e->h_cfg.size(),
+                                               e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1, e->spill());
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->ev_reset, c));
+    HIPCHK(e, hipStreamWaitEvent(s, e->ev_reset, 0));
+    return RL_OK;
+}
+
 // Launch every kernel once at creation, on batches of requests that are all
 // rejected (no config is registered yet), so no table entry is touched: HIP
 // loads kernels lazily, and a server's first batch on either path (k_small, or
@@ -1400,6 +1422,10 @@ static int warm_up(rl_engine* e) {
     }
     {   // the read-only query kernel
         const int r = run_peek(e, 1, a, s, false);
+        if (r != RL_OK) return r;
+    }
+    {   // the batched Reset: no config is registered yet, so the request is rejected
+        const int r = run_reset_batch(e, 1, e->d_key, e->d_ts, e->d_cfgid, e->d_dec, s, false);
         if (r != RL_OK) return r;
     }
     // the table count / GC / key listing kernels, on empty ranges: a server's
@@ -1579,6 +1605,38 @@ extern "C" int rl_reset(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t 
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return RL_OK;
 }
+
+// Many resets in one launch (rl_reset.h), ordered as rl_reset_device.  The
+// grid strides over any m: no chunking on the device entry point.
+extern "C" int rl_reset_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                     const uint32_t* cfg_id, uint8_t* status, void* stream) {
+    if (!e || (m && (!key_id || !ts_ns || !cfg_id))) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    return run_reset_batch(e, m, key_id, ts_ns, cfg_id, status, s, (e->flags & RL_OPT_PIPELINE) != 0);
+}
+
+extern "C" int rl_reset_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                              const uint32_t* cfg_id, uint8_t* status) {
+    if (!e || (m && (!key_id || !ts_ns || !cfg_id))) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    // chunks of max_batch: the size of the host API's staging arrays
+    for (size_t off = 0; off < m; off += e->max_batch) {
+        const uint32_t c = (uint32_t)std::min<size_t>(e->max_batch, m - off);
+        HIPCHK(e, hipMemcpyAsync(e->d_key, key_id + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(e->d_ts, ts_ns + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(e->d_cfgid, cfg_id + off, 4 * (size_t)c, hipMemcpyHostToDevice, s));
+        // the staged inputs arrive on s: the kernel always waits for them
+        const int r = run_reset_batch(e, c, e->d_key, e->d_ts, e->d_cfgid, status ? e->d_dec : nullptr, s, false);
+        if (r != RL_OK) return r;
+        if (status) HIPCHK(e, hipMemcpyAsync(status + off, e->d_dec, c, hipMemcpyDeviceToHost, s));
+        HIPCHK(e, hipStreamSynchronize(s));
+    }
+    return RL_OK;
+}
+
+extern "C" int rl_reset_grid_cap(void) { return RESET_GRID * RESET_BLOCK; }
 
 // Read-only queries (rl_peek.h).  Ordering as rl_reset_device: one kernel on
 // `chain` is after every batch enqueued before the call and before every one

@@ -147,14 +147,32 @@ public:
         ok &= hipEventRecord(d.ev, os_) == hipSuccess;
         return ok ? RL_OK : RL_EDEVICE;
     }
-    int launch_reset(int i, Slot& s, uint32_t cfg, uint64_t key, int64_t ts) override {
+    int launch_reset_batch(int i, Slot& s) override {
         (void)hipSetDevice(dev_id_);   // the submitter thread
-        s.t_h2d = steady_ns();
-        // enqueued on the engine's replay stream between two batches; the
+        Dev& d = dev_[i];
+        const size_t m = s.m;
+        // one kernel on the engine's replay stream between two batches; the
         // output stream (and so this slot's completion event) waits for it
-        const int rc = rl_reset_device(e_, cfg, key, ts, os_);
+        if (m <= zero_copy_max_) {
+            s.t_h2d = steady_ns();
+            const int rc = rl_reset_batch_device(e_, m, s.key, s.ts, s.cfg, s.dec, os_);
+            if (rc != RL_OK) return rc;
+            return hipEventRecord(d.ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
+        }
+        Slot dv;
+        carve(d.key, M_, dv);
+        bool ok = hipMemcpyAsync(dv.key, s.key, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+        ok &= hipMemcpyAsync(dv.ts, s.ts, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+        ok &= hipMemcpyAsync(dv.cfg, s.cfg, 4 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+        ok &= hipEventRecord(d.ev_in, cs_) == hipSuccess;
+        ok &= await_event(d.ev_in) == hipSuccess;
+        if (!ok) return RL_EDEVICE;
+        s.t_h2d = steady_ns();
+        const int rc = rl_reset_batch_device(e_, m, dv.key, dv.ts, dv.cfg, dv.dec, os_);
         if (rc != RL_OK) return rc;
-        return hipEventRecord(dev_[i].ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
+        ok = hipMemcpyAsync(s.dec, dv.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
+        ok &= hipEventRecord(d.ev, os_) == hipSuccess;
+        return ok ? RL_OK : RL_EDEVICE;
     }
     int wait(int i, Slot&) override {
         (void)hipSetDevice(dev_id_);   // the completer thread
@@ -246,9 +264,18 @@ public:
         s.t_h2d = steady_ns();
         return b_.batch(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset);
     }
-    int launch_reset(int, Slot& s, uint32_t cfg, uint64_t key, int64_t ts) override {
+    int launch_reset_batch(int, Slot& s) override {
         s.t_h2d = steady_ns();
-        return b_.reset ? b_.reset(b_.user, cfg, key, ts) : RL_EINVAL;
+        if (b_.reset_batch) return b_.reset_batch(b_.user, s.m, s.key, s.ts, s.cfg, s.dec);
+        if (!b_.reset) return RL_EINVAL;
+        // a backend without reset_batch: one reset call per key, in order; its
+        // RL_EINVAL (unknown config, reserved key) is that request's status
+        for (size_t i = 0; i < s.m; i++) {
+            const int rc = b_.reset(b_.user, s.cfg[i], s.key[i], s.ts[i]);
+            if (rc != RL_OK && rc != RL_EINVAL) return rc;
+            s.dec[i] = rc == RL_OK ? RL_RESET_DONE : RL_INVALID;
+        }
+        return RL_OK;
     }
     int launch_peek(int, Slot& s) override {
         s.t_h2d = steady_ns();
@@ -333,7 +360,8 @@ void Coalescer::SetNotify(NotifyFn fn, void* user) {
 
 int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
                       uint64_t* ticket, int64_t deadline, void* tag, Op op) {
-    if (!ticket || (m && (!key || !ts || !n || !cfg)) || deadline < 0 || !has_requests(op)) return RL_EINVAL;
+    if (!ticket || (m && (!key || !ts || !cfg || (!n && op != OP_RESET))) || deadline < 0 || !is_batched(op))
+        return RL_EINVAL;
     Sub* s = get_sub(m);
     s->op = op;
     s->deadline = deadline;
@@ -341,11 +369,12 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
     if (trace_cap_) s->submit_ns = steady_ns();
     memcpy(s->key, key, 8 * m);
     memcpy(s->ts, ts, 8 * m);
-    memcpy(s->n, n, 8 * m);
+    if (n) memcpy(s->n, n, 8 * m);
     memcpy(s->cfg, cfg, 4 * m);
     {
         std::lock_guard<std::mutex> g(mu_);
-        if (stop_ || pending_ + m > o_.queue_cap) {
+        // a Reset is never turned away by a full queue
+        if (stop_ || (pending_ + m > o_.queue_cap && op != OP_RESET)) {
             const int rc = stop_ ? RL_ECLOSED : RL_EAGAIN;
             put_sub(s);
             return rc;
@@ -504,7 +533,9 @@ int Coalescer::Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* 
     // done and applied: no slot or queue references it any more
     lk.unlock();
     const size_t m = s->m;
-    if (has_requests(s->op)) {
+    if (s->op == OP_RESET) {
+        if (dec) memcpy(dec, s->dec, m);   // the per-request status
+    } else if (has_requests(s->op)) {
         if (dec) memcpy(dec, s->dec, m);
         if (rem) memcpy(rem, s->rem, 8 * m);
         if (retry) memcpy(retry, s->retry, 8 * m);
@@ -714,83 +745,74 @@ void Coalescer::submitter() {
         const int si = next_slot_;
         Slot& s = slots_[si];
         s.parts.clear();
-        s.is_reset = false;
+        // resets: the run of adjacent reset submissions at the queue head is
+        // one launch, enqueued between the batches around it
+        s.is_reset = f->op == OP_RESET;
         s.is_peek = f->op == OP_PEEK;
         size_t m = 0;
-        if (f->op == OP_RESET) {
-            // like a one-request batch: enqueued between the batches around it
-            queue_.pop_front();
-            f->in_queue = false;
-            f->taken = 1;
-            f->inflight = 1;
-            pending_ -= 1;
-            s.parts.push_back({f, 0, 1, 0});
-            s.is_reset = true;
-        } else {
-            const int64_t now = steady_ns();
-            while (m < o_.max_batch && !queue_.empty()) {
-                Sub* sub = queue_.front();
-                if (sub->dropped) {
-                    queue_.pop_front();
-                    sub->in_queue = false;
-                    maybe_free_locked(sub);
-                    continue;
-                }
-                // requests merge; a peek submission is launched on its own
-                if (sub->op != f->op || (s.is_peek && sub != f)) break;
-                if (sub->taken < sub->m && (sub->cancelled || (sub->deadline && sub->deadline <= now))) {
-                    // its context ended before (the rest of) it was sent: that part is never applied
-                    if (sub->taken == 0) drop_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
-                    else truncate_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
-                }
-                if (sub->dropped || sub->taken == sub->m) {
-                    // dropped, or the rest of a split submission truncated: nothing left to launch
-                    queue_.pop_front();
-                    sub->in_queue = false;
-                    maybe_free_locked(sub);
-                    continue;
-                }
-                const size_t take = std::min(sub->m - sub->taken, (size_t)o_.max_batch - m);
-                s.parts.push_back({sub, sub->taken, take, m});
-                sub->taken += take;
-                sub->inflight++;
-                m += take;
-                if (sub->taken == sub->m) {
-                    queue_.pop_front();
-                    sub->in_queue = false;
-                }
+        const int64_t now = steady_ns();
+        while (m < o_.max_batch && !queue_.empty()) {
+            Sub* sub = queue_.front();
+            if (sub->dropped) {
+                queue_.pop_front();
+                sub->in_queue = false;
+                maybe_free_locked(sub);
+                continue;
             }
-            if (m == 0) continue;   // everything at the head was dropped
-            pending_ -= m;
+            // requests merge, and so do resets; a peek submission is launched on its own
+            if (sub->op != f->op || (s.is_peek && sub != f)) break;
+            if (sub->taken < sub->m && (sub->cancelled || (sub->deadline && sub->deadline <= now))) {
+                // its context ended before (the rest of) it was sent: that part is never applied
+                if (sub->taken == 0) drop_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
+                else truncate_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
+            }
+            if (sub->dropped || sub->taken == sub->m) {
+                // dropped, or the rest of a split submission truncated: nothing left to launch
+                queue_.pop_front();
+                sub->in_queue = false;
+                maybe_free_locked(sub);
+                continue;
+            }
+            const size_t take = std::min(sub->m - sub->taken, (size_t)o_.max_batch - m);
+            s.parts.push_back({sub, sub->taken, take, m});
+            sub->taken += take;
+            sub->inflight++;
+            m += take;
+            if (sub->taken == sub->m) {
+                queue_.pop_front();
+                sub->in_queue = false;
+            }
         }
+        if (m == 0) continue;   // everything at the head was dropped
+        pending_ -= m;
         next_slot_ = (next_slot_ + 1) % (int)o_.max_in_flight;
         inflight_++;
         lk.unlock();
         if (trace_cap_) s.t_form = steady_ns();
+        // the submissions' inputs are immutable after Submit: copy unlocked
+        for (const auto& p : s.parts) {
+            memcpy(s.key + p.at, p.sub->key + p.off, 8 * p.count);
+            memcpy(s.ts + p.at, p.sub->ts + p.off, 8 * p.count);
+            if (!s.is_reset) memcpy(s.n + p.at, p.sub->n + p.off, 8 * p.count);
+            memcpy(s.cfg + p.at, p.sub->cfg + p.off, 4 * p.count);
+        }
+        s.m = m;
         if (s.is_reset) {
-            const Sub* r = s.parts[0].sub;
-            s.m = 0;
-            s.status = be_->launch_reset(si, s, r->cfg[0], r->key[0], r->ts[0]);
+            // inserts nothing: no part in the automatic GC's budgets
+            s.status = be_->launch_reset_batch(si, s);
+        } else if (s.is_peek) {
+            // inserts nothing: no part in the automatic GC's budgets
+            s.status = be_->launch_peek(si, s);
         } else {
-            // the submissions' inputs are immutable after Submit: copy unlocked
-            for (const auto& p : s.parts) {
-                memcpy(s.key + p.at, p.sub->key + p.off, 8 * p.count);
-                memcpy(s.ts + p.at, p.sub->ts + p.off, 8 * p.count);
-                memcpy(s.n + p.at, p.sub->n + p.off, 8 * p.count);
-                memcpy(s.cfg + p.at, p.sub->cfg + p.off, 4 * p.count);
-            }
-            s.m = m;
-            if (s.is_peek) {
-                // inserts nothing: no part in the automatic GC's budgets
-                s.status = be_->launch_peek(si, s);
-            } else {
-                auto_gc(s);
-                s.status = be_->launch(si, s);
-            }
+            auto_gc(s);
+            s.status = be_->launch(si, s);
         }
         if (trace_cap_) s.t_launched = steady_ns();
         lk.lock();
-        if (!s.is_peek) {
+        if (s.is_reset) {
+            st_.batches++;          // a launch, but no request batch: max_batch_seen stays
+            st_.reset_launches++;
+        } else if (!s.is_peek) {
             st_.batches++;
             st_.max_batch_seen = std::max<uint64_t>(st_.max_batch_seen, m);
         }
@@ -822,7 +844,13 @@ void Coalescer::completer() {
         Slot& s = slots_[si];
         const int64_t t_wait = trace_cap_ ? steady_ns() : 0;
         int st = s.status == RL_OK ? be_->wait(si, s) : s.status;
-        if (!s.is_reset) {
+        uint64_t nreset = 0;
+        if (s.is_reset) {
+            if (st == RL_OK) {
+                for (const auto& p : s.parts) memcpy(p.sub->dec + p.off, s.dec + p.at, p.count);
+                for (size_t i = 0; i < s.m; i++) nreset += s.dec[i] == RL_RESET_DONE;
+            }
+        } else {
             for (const auto& p : s.parts) {
                 memcpy(p.sub->dec + p.off, s.dec + p.at, p.count);
                 memcpy(p.sub->rem + p.off, s.rem + p.at, 8 * p.count);
@@ -845,7 +873,8 @@ void Coalescer::completer() {
             }
             done_batches_++;
             if (s.is_peek) st_.peeked += s.m;
-            else st_.decided += s.is_reset ? 1 : s.m;
+            else if (s.is_reset) st_.resets += nreset;
+            else st_.decided += s.m;
             for (const auto& p : s.parts) {
                 Sub* sub = p.sub;
                 if (st != RL_OK && !sub->truncated) sub->status = st;
@@ -901,9 +930,10 @@ extern "C" int rl_coalescer_create(rl_engine* e, const rl_coalescer_opts* opts, 
 
 extern "C" int rl_coalescer_create_with_host_backend(const rl_coalescer_backend* be, const rl_coalescer_opts* opts,
                                                      rl_coalescer** out) {
-    // a caller compiled before `peek` was added passes the shorter struct
+    // a caller compiled before `peek` / `reset_batch` were added passes the shorter struct
     if (!be || !out ||
-        (be->struct_size != sizeof(rl_coalescer_backend) && be->struct_size != offsetof(rl_coalescer_backend, peek)))
+        (be->struct_size != sizeof(rl_coalescer_backend) && be->struct_size != offsetof(rl_coalescer_backend, peek) &&
+         be->struct_size != offsetof(rl_coalescer_backend, reset_batch)))
         return RL_EINVAL;
     rl_coalescer_backend b{};
     memcpy(&b, be, be->struct_size);
@@ -919,7 +949,7 @@ extern "C" int rl_coalescer_create_with_backend(rl_batch_fn fn, void* user, cons
 
 extern "C" int rl_coalescer_create_with_backends(rl_batch_fn fn, rl_reset_fn reset_fn, void* user,
                                                  const rl_coalescer_opts* opts, rl_coalescer** out) {
-    rl_coalescer_backend b{sizeof(rl_coalescer_backend), fn, reset_fn, nullptr, nullptr, user, nullptr};
+    rl_coalescer_backend b{sizeof(rl_coalescer_backend), fn, reset_fn, nullptr, nullptr, user, nullptr, nullptr};
     return rl_coalescer_create_with_host_backend(&b, opts, out);
 }
 
@@ -978,7 +1008,19 @@ extern "C" int rl_coalescer_reset(rl_coalescer* c, uint64_t key_id, int64_t ts_n
     uint64_t t;
     int rc = c->c->SubmitOp(rlc::OP_RESET, key_id, ts_ns, cfg_id, 0, 0, 0, &t);
     if (rc != RL_OK) return rc;
-    return c->c->Wait(t, -1, nullptr, nullptr, nullptr, nullptr);
+    // merged with the resets queued next to it: its own status tells whether it ran
+    uint8_t status = RL_RESET_DONE;
+    rc = c->c->Wait(t, -1, &status, nullptr, nullptr, nullptr);
+    return rc == RL_OK && status != RL_RESET_DONE ? RL_EINVAL : rc;
+}
+
+extern "C" int rl_coalescer_reset_batch(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                        const uint32_t* cfg_id, uint8_t* status) {
+    if (!c) return RL_EINVAL;
+    uint64_t t;
+    int rc = c->c->Submit(m, key_id, ts_ns, nullptr, cfg_id, &t, 0, nullptr, rlc::OP_RESET);
+    if (rc != RL_OK) return rc;
+    return c->c->Wait(t, -1, status, nullptr, nullptr, nullptr);
 }
 
 extern "C" int rl_coalescer_peek(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,

@@ -36,7 +36,7 @@ struct Slot {
     int64_t* retry = nullptr;
     int64_t* reset = nullptr;
     size_t m = 0;
-    bool is_reset = false;   // a Reset (parts[0].sub), not requests
+    bool is_reset = false;   // resets (a run of adjacent OP_RESET submissions): key / ts / cfg in, status in `dec`
     bool is_peek = false;    // read-only queries (one OP_PEEK submission, or a part of it)
     int status = RL_OK;
     int64_t t_form = 0, t_h2d = 0, t_launched = 0;   // steady ns (batch trace)
@@ -53,9 +53,10 @@ public:
     virtual ~Backend() = default;
     virtual int init(int nslots, size_t max_batch, std::vector<Slot>* slots) = 0;
     virtual int launch(int slot, Slot& s) = 0;   // asynchronous
-    // Reset after every launched batch and before every later one,
-    // asynchronous like a launch (completes through wait(slot))
-    virtual int launch_reset(int slot, Slot& s, uint32_t cfg, uint64_t key, int64_t ts) = 0;
+    // the slot's s.m resets (key, ts, cfg; rl_reset_batch_device) after every
+    // launched batch and before every later one, asynchronous like a launch
+    // (completes through wait(slot)); per-request status into s.dec
+    virtual int launch_reset_batch(int slot, Slot& s) = 0;
     // read-only queries (rl_peek_batch_device) on the slot's staging arrays,
     // ordered and completed like a launch
     virtual int launch_peek(int slot, Slot& s) = 0;
@@ -85,6 +86,9 @@ std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b);
 enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE };
 // submissions that carry requests and results (the rest carry one operation)
 inline bool has_requests(Op op) { return op == OP_REQ || op == OP_PEEK; }
+// submissions the submitter takes from the queue in parts of up to max_batch:
+// requests and results, or resets (key / ts / cfg) and their status in `dec`
+inline bool is_batched(Op op) { return op <= OP_PEEK; }
 // the synchronous table operations (run_table_op)
 inline bool is_table_op(Op op) { return op >= OP_INFO; }
 
@@ -151,10 +155,13 @@ public:
     // tag: with SetNotify, the completion callback receives it
     // op: OP_REQ, or OP_PEEK -- read-only queries, queued in sequence order
     // like a Reset and launched on their own (not merged with requests or
-    // with other peeks); not counted in submitted / decided
+    // with other peeks); not counted in submitted / decided --, or OP_RESET:
+    // m resets (n is not read), merged with the reset submissions next to it
+    // in the queue into one launch; Wait's `dec` receives their status
     int Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
                uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr, Op op = OP_REQ);
-    // a Reset / table count / table GC / snapshot / restore, queued in sequence order
+    // a single Reset (an OP_RESET submission of one) / table count / table GC /
+    // snapshot / restore, queued in sequence order
     int SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
                  uint64_t cap_win, uint64_t* ticket, void* tag = nullptr, const SnapArgs* snap = nullptr);
     // Completion callback for submissions made with a tag: fn(user, ticket,

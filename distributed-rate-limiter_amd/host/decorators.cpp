@@ -135,6 +135,12 @@ Error LoggingDecorator::ResetAt(const Context& ctx, const std::string& key, int6
     return e;
 }
 
+Error LoggingDecorator::ResetManyAt(const Context& ctx, const std::vector<std::string>& keys, int64_t t) {
+    Error e = inner_->ResetManyAt(ctx, keys, t);
+    if (e) sink_(LogLevel::Error, "rate limiter reset error", {{"keys", std::to_string(keys.size())}, {"error", e.msg}});
+    return e;
+}
+
 void LoggingDecorator::BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                                   std::vector<BatchOutcome>* out) {
     inner_->BatchAllow(ctx, reqs, out);

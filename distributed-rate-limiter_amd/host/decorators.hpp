@@ -36,6 +36,9 @@ public:
     Error AllowN(const Context& ctx, const std::string& key, int64_t n, Result* out) override;
     Error Reset(const Context& ctx, const std::string& key) override;
     Error ResetAt(const Context& ctx, const std::string& key, int64_t t) override;
+    Error ResetManyAt(const Context& ctx, const std::vector<std::string>& keys, int64_t t) override {
+        return inner_->ResetManyAt(ctx, keys, t);
+    }
     Error Close() override { return inner_->Close(); }
     // a peek is no decision: forwarded, not counted
     Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) override {
@@ -76,6 +79,8 @@ public:
     Error AllowN(const Context& ctx, const std::string& key, int64_t n, Result* out) override;
     Error Reset(const Context& ctx, const std::string& key) override;
     Error ResetAt(const Context& ctx, const std::string& key, int64_t t) override;
+    // one "rate limiter reset error" record for the whole call on failure
+    Error ResetManyAt(const Context& ctx, const std::vector<std::string>& keys, int64_t t) override;
     Error Close() override { return inner_->Close(); }
     // a peek is no decision: forwarded, not logged
     Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) override {

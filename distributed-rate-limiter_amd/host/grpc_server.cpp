@@ -211,7 +211,8 @@ struct Limiter {
 struct Io;
 struct Conn;
 
-enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK };   // K_PEEK: a read-only AllowN (rl_coalescer_peek)
+// K_PEEK: a read-only AllowN (rl_coalescer_peek); K_RESET_BATCH: many resets, one coalescer submission
+enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH };
 
 struct Stream {
     int32_t id = 0;
@@ -419,7 +420,25 @@ void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, c
     Stream* st = it->second.get();
     st->pending = false;
     std::string msg;
+    if (rpc.kind == K_RESET_BATCH) {
+        // ResetBatchResponse.errors = 1: one string per request, "" = done
+        size_t j = 0;
+        for (const BatchItem& b : rpc.items) {
+            std::string e;
+            if (b.err == 1) e = "unknown limiter " + py_repr(b.name);
+            else {
+                const int one = rc != RL_OK ? rc : (dec && dec[j] == RL_RESET_DONE) ? RL_OK : RL_EINVAL;
+                if (one != RL_OK) e = "failed to reset rate limit: engine status " + std::to_string(one);
+                j++;
+            }
+            put_varint(msg, (1u << 3) | 2);   // an empty string is an entry too
+            put_varint(msg, e.size());
+            msg += e;
+        }
+        return respond_ok(c, st, msg);
+    }
     if (rpc.kind == K_RESET) {
+        if (rc == RL_OK && dec && dec[0] != RL_RESET_DONE) rc = RL_EINVAL;
         if (rc != RL_OK) respond_err(c, st, GRPC_UNAVAILABLE, "failed to reset rate limit: engine status " + std::to_string(rc));
         else respond_ok(c, st, msg);
         return;
@@ -457,7 +476,7 @@ void collect(Io* io, uint64_t ticket) {
     auto it = io->rpcs.find(ticket);
     if (it == io->rpcs.end()) return;   // already collected (a deadline, a cancel)
     Rpc& rpc = it->second;
-    const size_t m = rpc.kind == K_RESET ? 0 : rpc.m;
+    const size_t m = rpc.kind == K_RESET ? 1 : rpc.m;   // a Reset's ticket carries its one status
     std::vector<uint8_t> dec(m);
     std::vector<int64_t> rem(m), retry(m), reset(m);
     const int rc = io->srv->co->Wait(ticket, 0, dec.data(), rem.data(), retry.data(), reset.data());
@@ -475,8 +494,10 @@ void submit_rpc(Io* io, Conn* c, Stream* st, Rpc&& rpc, size_t m, const uint64_t
     uint64_t ticket = 0;
     int rc;
     if (rpc.kind == K_RESET) rc = s->co->SubmitOp(rlc::OP_RESET, key[0], ts[0], cfg[0], 0, 0, 0, &ticket, io);
+    // like a Reset, a reset batch has no deadline: once queued it is applied
+    else if (rpc.kind == K_RESET_BATCH) rc = s->co->Submit(m, key, ts, nullptr, cfg, &ticket, 0, io, rlc::OP_RESET);
     else rc = s->co->Submit(m, key, ts, n, cfg, &ticket, rpc.deadline, io, rpc.kind == K_PEEK ? rlc::OP_PEEK : rlc::OP_REQ);
-    if (rpc.kind != K_PEEK) s->n_dec += m;   // a peek decides nothing
+    if (rpc.kind != K_PEEK && rpc.kind != K_RESET_BATCH) s->n_dec += m;   // a peek or a reset decides nothing
     if (rc != RL_OK) {   // queue full / closed: the error branch at once
         finish_rpc(io, 0, rpc, rc, nullptr, nullptr, nullptr, nullptr);
         return;
@@ -505,6 +526,39 @@ void dispatch(Conn* c, Stream* st) {
         std::string out;
         put_int(out, 1, status);
         return respond_ok(c, st, out);
+    }
+    if (p == "/ratelimiter.v1.RateLimiterAdmin/ResetBatch") {
+        // one coalescer submission per RPC, completed through the ticket's
+        // notification like every other RPC: the event loop never blocks
+        Rpc rpc{c, st->id, K_RESET_BATCH, s->now(), 0, nullptr, {}, 0};
+        std::vector<uint64_t> key;
+        std::vector<int64_t> ts;
+        std::vector<uint32_t> cfg;
+        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
+        while (pb.more()) {
+            const uint64_t tag = pb.varint();
+            if ((tag >> 3) != 1 || (tag & 7) != 2) {
+                pb.skip((uint32_t)(tag & 7));
+                continue;
+            }
+            ReqMsg r;
+            if (!parse_req(pb.bytes(), &r) || !pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad ResetBatchRequest");
+            BatchItem it{s->find(r.limiter), 0, 0, {}};
+            if (!it.lim) {
+                it.err = 1;
+                it.name = std::string(r.limiter);
+            } else {
+                key.push_back(s->key_id(it.lim, r.key));
+                ts.push_back(rpc.t);
+                cfg.push_back(it.lim->cfg);
+            }
+            rpc.items.push_back(std::move(it));
+        }
+        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad ResetBatchRequest");
+        rpc.m = key.size();
+        if (rpc.m == 0) return finish_rpc(io, 0, rpc, RL_OK, nullptr, nullptr, nullptr, nullptr);
+        const size_t mm = rpc.m;
+        return submit_rpc(io, c, st, std::move(rpc), mm, key.data(), ts.data(), nullptr, cfg.data());
     }
     static const std::string peek_path = "/ratelimiter.v1.RateLimiterStatus/Peek";
     const bool is_peek = p == peek_path;

@@ -347,6 +347,27 @@ public:
         return Error{};
     }
 
+    Error ResetManyAt(const Context& ctx, const std::vector<std::string>& keys, int64_t t) override {
+        (void)ctx;
+        if (closed_.load())
+            return Error::New(Error::Other, "failed to reset rate limit: engine: client is closed");
+        const size_t m = keys.size();
+        std::vector<uint64_t> id(m);
+        std::vector<int64_t> ts(m);
+        for (size_t i = 0; i < m; i++) {
+            id[i] = eng_->Intern(cfg_.FormatKey(keys[i]));
+            ts[i] = t == INT64_MIN ? eng_->clock() : t;
+        }
+        const std::vector<uint32_t> cfg(m, cfg_id_);
+        std::lock_guard<std::mutex> g(eng_->mu());
+        // interned ids are never the reserved key and the config is registered:
+        // every request of the batch is executed
+        const int rc = rl_reset_batch(eng_->raw(), m, id.data(), ts.data(), cfg.data(), nullptr);
+        if (rc != RL_OK)
+            return Error::New(Error::Other, "failed to reset rate limit: " + engine_error(eng_->raw(), rc));
+        return Error{};
+    }
+
     Error Close() override {
         closed_.store(true);
         return Error{};
@@ -697,6 +718,21 @@ extern "C" int rll_reset(rll_limiter* l, const char* key, size_t keylen, int64_t
     std::string k(key ? key : "", keylen);
     Error e = now_ns == RLL_NOW_WALL ? l->lim->Reset(Context::Background(), k)
                                      : l->lim->ResetAt(Context::Background(), k, now_ns);
+    if (e) {
+        put_err(err, errlen, e.msg);
+        return RLL_ERR_RESET;
+    }
+    return RLL_OK;
+}
+
+extern "C" int rll_reset_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens,
+                              int64_t now_ns, char* err, size_t errlen) {
+    if (!l || (m && (!keys || !keylens))) return RLL_ERR_ARG;
+    for (size_t i = 0; i < m; i++)
+        if (!keys[i] && keylens[i]) return RLL_ERR_ARG;
+    std::vector<std::string> ks(m);
+    for (size_t i = 0; i < m; i++) ks[i].assign(keys[i] ? keys[i] : "", keylens[i]);
+    const Error e = l->lim->ResetManyAt(Context::Background(), ks, now_ns == RLL_NOW_WALL ? INT64_MIN : now_ns);
     if (e) {
         put_err(err, errlen, e.msg);
         return RLL_ERR_RESET;

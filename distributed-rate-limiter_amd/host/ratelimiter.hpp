@@ -146,6 +146,10 @@ public:
     virtual Error Reset(const Context& ctx, const std::string& key) = 0;
     // Reset as if called at Unix time t (deterministic replay)
     virtual Error ResetAt(const Context& ctx, const std::string& key, int64_t t) = 0;
+    // ResetMany (new; rl_reset_batch): Reset of every key, in one engine
+    // launch.  t = INT64_MIN reads the engine clock once per key, as that
+    // many Reset calls would.
+    virtual Error ResetManyAt(const Context& ctx, const std::vector<std::string>& keys, int64_t t) = 0;
     virtual Error Close() = 0;
     // Peek (new; rl_peek_batch): the Result AllowN(key, n) would return at
     // now_ns (INT64_MIN: the engine clock), changing nothing.  n == 0 asks how

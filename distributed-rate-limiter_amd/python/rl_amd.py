@@ -30,6 +30,7 @@ TOKEN_BUCKET, SLIDING_WINDOW, FIXED_WINDOW = 1, 2, 3
 ALG_BY_NAME = {"token_bucket": TOKEN_BUCKET, "sliding_window": SLIDING_WINDOW, "fixed_window": FIXED_WINDOW}
 PROFILE_REDIS7, PROFILE_MINIREDIS = 0, 1
 DENIED, ALLOWED, ERROR, INVALID = 0, 1, 2, 3
+RESET_DONE = 1   # per-request status of a reset batch (RL_RESET_DONE; RL_INVALID otherwise)
 KEY_RESERVED = (1 << 64) - 1
 
 RLL_OK, RLL_ERR_INVALID_N, RLL_ERR_FAILED, RLL_ERR_CONFIG, RLL_ERR_RESET, RLL_ERR_ARG = 0, 1, 2, 3, 4, 5
@@ -117,20 +118,22 @@ class rl_coalescer_opts(_Sized):
 class rl_coalescer_stats(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("pad_", C.c_uint32)] + [
         (k, C.c_uint64) for k in ("submitted", "decided", "batches", "max_batch_seen", "pending", "expired",
-                                  "cancelled", "gc_runs", "gc_checks", "gc_failures", "peeked")]
+                                  "cancelled", "gc_runs", "gc_checks", "gc_failures", "peeked", "resets",
+                                  "reset_launches")]
 
 
 vp = C.c_void_p
 # rl_batch_fn (include/rl_coalescer.h)
 BATCH_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp)
 RESET_FN = C.CFUNCTYPE(C.c_int, vp, C.c_uint32, C.c_uint64, C.c_int64)
+RESET_BATCH_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp)
 INFO_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.POINTER(rl_table_info))
 GC_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(rl_table_info))
 
 
 class rl_coalescer_backend(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("batch", BATCH_FN), ("reset", RESET_FN), ("table_info", INFO_FN),
-                ("gc", GC_FN), ("user", vp), ("peek", BATCH_FN)]
+                ("gc", GC_FN), ("user", vp), ("peek", BATCH_FN), ("reset_batch", RESET_BATCH_FN)]
 
 _sig = {
     "rl_engine_create": (C.c_int, [C.POINTER(rl_opts), C.POINTER(vp)]),
@@ -144,6 +147,9 @@ _sig = {
     "rl_coalescer_peek": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
     "rll_peek_n": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int,
                              C.POINTER(rll_result), C.c_char_p, C.c_size_t]),
+    "rl_reset_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
+    "rl_reset_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
+    "rl_reset_grid_cap": (C.c_int, []),
     "rl_engine_sync": (C.c_int, [vp]),
     "rl_reset": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int64]),
     "rl_reset_device": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int64, vp]),
@@ -181,6 +187,7 @@ _sig = {
                               C.POINTER(rll_result), C.c_char_p, C.c_size_t]),
     "rll_allow_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp, vp]),
     "rll_reset": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int64, C.c_char_p, C.c_size_t]),
+    "rll_reset_many": (C.c_int, [vp, C.c_size_t, vp, vp, C.c_int64, C.c_char_p, C.c_size_t]),
     "rll_close": (C.c_int, [vp]),
     "rll_free": (C.c_int, [vp]),
     "rll_new_allowed_result": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(rll_result)]),
@@ -198,6 +205,7 @@ _sig = {
     "rl_coalescer_create_with_host_backend": (C.c_int, [C.POINTER(rl_coalescer_backend),
                                                         C.POINTER(rl_coalescer_opts), C.POINTER(vp)]),
     "rl_coalescer_reset": (C.c_int, [vp, C.c_uint64, C.c_int64, C.c_uint32]),
+    "rl_coalescer_reset_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
     "rl_coalescer_now_ns": (C.c_int64, []),
     "rl_coalescer_submit_deadline": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, C.c_int64, C.POINTER(C.c_uint64)]),
     "rl_coalescer_cancel": (C.c_int, [vp, C.c_uint64]),
@@ -265,6 +273,8 @@ class Decisions:
 OPT_PIPELINE = 1
 # requests one k_peek launch covers at one request per thread (grid cap x block size)
 PEEK_GRID_CAP = lib.rl_peek_grid_cap()
+# the same of k_reset_batch
+RESET_GRID_CAP = lib.rl_reset_grid_cap()
 
 
 class Engine:
@@ -378,6 +388,26 @@ class Engine:
 
     def reset(self, cfg: int, key: int, ts: int):
         rc = lib.rl_reset(self.h, cfg, key, ts)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def reset_batch(self, key, ts, cfg, want_status=True):
+        """rl_reset_batch: m resets in one launch (chunks of max_batch), with
+        the effect of m reset() calls in any order -> the per-request status
+        (RESET_DONE, or INVALID for an unknown config / the reserved key)"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        m = key.size
+        assert ts.size == m and cfg.size == m
+        status = np.empty(m, np.uint8) if want_status else None
+        rc = lib.rl_reset_batch(self.h, m, _ptr(key), _ptr(ts), _ptr(cfg), _ptr(status))
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        return status
+
+    def reset_batch_device(self, m, key_p, ts_p, cfg_p, status_p=None, stream=None):
+        rc = lib.rl_reset_batch_device(self.h, m, key_p, ts_p, cfg_p, status_p, stream)
         if rc != RL_OK:
             raise EngineError(rc, self.last_error())
 
@@ -752,6 +782,17 @@ class RateLimiter:
         rc = lib.rll_reset(self.h, kb, len(kb), now_ns, buf, 512)
         return None if rc == RLL_OK else buf.value.decode()
 
+    def reset_many(self, keys, now_ns=NOW_WALL):
+        """rll_reset_many: Reset of every key, one engine launch -> error
+        message | None"""
+        m = len(keys)
+        kbs = [k.encode() for k in keys]
+        arr = (C.c_char_p * m)(*kbs)
+        lens = np.array([len(k) for k in kbs], np.uint64)
+        buf = C.create_string_buffer(512)
+        rc = lib.rll_reset_many(self.h, m, C.cast(arr, vp), _ptr(lens), now_ns, buf, 512)
+        return None if rc == RLL_OK else buf.value.decode()
+
     def close(self):
         lib.rll_close(self.h)
 
@@ -787,13 +828,14 @@ class Coalescer:
     into engine batches.  `engine` is an Engine (GPU) or, for the CPU tests of
     the batching logic, a Python function with rl_decide_batch's host-array
     signature (the test seam rl_coalescer_create_with_host_backend; `reset`,
-    `table_info`, `gc`: the other backend functions, optional).
+    `table_info`, `gc`, `peek`, `reset_batch`: the other backend functions,
+    optional).
 
     gc_interval_ns > 0 turns on the automatic table GC (rl_coalescer_opts)."""
 
     def __init__(self, engine, max_batch=65536, max_in_flight=3, linger_ns=0, queue_cap=0, reset=None,
                  table_info=None, gc=None, peek=None, gc_interval_ns=0, gc_high_pct=0, gc_margin_ms=0,
-                 gc_max_tb_capacity=0, gc_max_win_capacity=0):
+                 gc_max_tb_capacity=0, gc_max_win_capacity=0, reset_batch=None):
         o = rl_coalescer_opts(max_batch=max_batch, max_in_flight=max_in_flight, gc_high_pct=gc_high_pct,
                               linger_ns=linger_ns, queue_cap=queue_cap, gc_interval_ns=gc_interval_ns,
                               gc_margin_ms=gc_margin_ms, gc_max_tb_capacity=gc_max_tb_capacity,
@@ -808,7 +850,8 @@ class Coalescer:
                 batch=BATCH_FN(engine), reset=RESET_FN(reset) if reset else C.cast(None, RESET_FN),
                 table_info=INFO_FN(table_info) if table_info else C.cast(None, INFO_FN),
                 gc=GC_FN(gc) if gc else C.cast(None, GC_FN), user=None,
-                peek=BATCH_FN(peek) if peek else C.cast(None, BATCH_FN))
+                peek=BATCH_FN(peek) if peek else C.cast(None, BATCH_FN),
+                reset_batch=RESET_BATCH_FN(reset_batch) if reset_batch else C.cast(None, RESET_BATCH_FN))
             rc = lib.rl_coalescer_create_with_host_backend(C.byref(self._be), C.byref(o), C.byref(h))
         if rc != RL_OK:
             raise EngineError(rc, "rl_coalescer_create failed")
@@ -843,6 +886,18 @@ class Coalescer:
 
     def reset(self, key, ts, cfg) -> int:
         return lib.rl_coalescer_reset(self.h, key, ts, cfg)
+
+    def reset_batch(self, key, ts, cfg):
+        """rl_coalescer_reset_batch: m resets as one submission in sequence
+        order; blocks until applied.  -> (rc, status): RESET_DONE or INVALID
+        per request"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        assert ts.size == key.size and cfg.size == key.size
+        status = np.empty(key.size, np.uint8)
+        rc = lib.rl_coalescer_reset_batch(self.h, key.size, _ptr(key), _ptr(ts), _ptr(cfg), _ptr(status))
+        return rc, status
 
     def peek(self, key, ts, n, cfg):
         """rl_coalescer_peek: read-only queries in sequence order; blocks.

@@ -205,5 +205,18 @@ def peek(stub, limiter: str, key: str, n: int = 0, **kw):
     return stub.Peek(api("ratelimiter.proto").AllowNRequest(limiter=limiter, key=key, n=n), **kw)
 
 
+def admin_stub(channel):
+    """the bulk administration service (RateLimiterAdmin: ResetBatch)"""
+    return Stub(channel, api("ratelimiter.proto"), "RateLimiterAdmin")
+
+
+def reset_batch(stub, pairs, **kw):
+    """RateLimiterAdmin.ResetBatch (stub: admin_stub(channel)) of (limiter, key)
+    pairs -> one error string per pair, "" = done"""
+    a = api("ratelimiter.proto")
+    req = a.ResetBatchRequest(requests=[a.ResetRequest(limiter=l, key=k) for l, k in pairs])
+    return list(stub.ResetBatch(req, **kw).errors)
+
+
 def health_stub(channel):
     return Stub(channel, api("health.proto"), "Health")

@@ -221,6 +221,35 @@ class RateLimiterService:
             ctx.abort(grpc.StatusCode.UNAVAILABLE, f"failed to reset rate limit: engine status {rc}")
         return self.a.ResetResponse()
 
+    def ResetBatch(self, req, ctx):
+        """many Reset calls: one reset_batch submission to the coalescer; an
+        unknown limiter is that entry's error string"""
+        rs = req.requests
+        t = self.clock()
+        errors = [""] * len(rs)
+        idx, keys, cfg = [], [], []
+        groups = {}
+        for i, r in enumerate(rs):
+            lim = self.by_name.get(r.limiter)
+            if lim is None:
+                errors[i] = f"unknown limiter {r.limiter!r}"
+                continue
+            groups.setdefault(r.limiter, []).append(len(idx))
+            idx.append(i)
+            keys.append(r.key.encode())
+            cfg.append(lim.cfg_id)
+        if idx:
+            kid = np.empty(len(idx), np.uint64)
+            for name, pos in groups.items():
+                kid[pos] = self._ids(self.by_name[name], [keys[p] for p in pos], len(pos))
+            rc, status = self.co.reset_batch(kid, np.full(len(idx), t, np.int64), np.array(cfg, np.uint32))
+            for j, i in enumerate(idx):
+                if rc != rl_amd.RL_OK:
+                    errors[i] = f"failed to reset rate limit: engine status {rc}"
+                elif status[j] != rl_amd.RESET_DONE:
+                    errors[i] = f"failed to reset rate limit: engine status {rl_amd.RL_EINVAL}"
+        return self.a.ResetBatchResponse(errors=errors)
+
     def AllowBatch(self, req, ctx):
         """many AllowN calls: one submission to the coalescer (one GPU batch
         when it fits); per-request errors in AllowResponse.error"""
@@ -266,6 +295,7 @@ def build_server(service: RateLimiterService, address: str, workers: int = 64) -
     server = grpc.server(futures.ThreadPoolExecutor(max_workers=workers),
                          options=[("grpc.so_reuseport", 0)])
     for a, sname, impl in ((service.a, "RateLimiter", service), (service.a, "RateLimiterStatus", service),
+                           (service.a, "RateLimiterAdmin", service),
                            (service.h, "Health", service)):
         handlers = {}
         for mname, inp, out in a.services[sname]:

@@ -105,6 +105,8 @@ typedef struct rl_coalescer_stats {
     uint64_t gc_checks;      /* automatic occupancy counts */
     uint64_t gc_failures;    /* GCs that returned an error (the old tables stay) */
     uint64_t peeked;         /* read-only queries completed (rl_coalescer_peek); not in submitted / decided */
+    uint64_t resets;         /* resets executed (rl_coalescer_reset / _reset_batch); not in submitted / decided */
+    uint64_t reset_launches; /* launches they took: a run of adjacent reset submissions is one launch */
 } rl_coalescer_stats;
 
 /* Signature of rl_decide_batch (host arrays, synchronous).  A backend of this
@@ -115,6 +117,9 @@ typedef int (*rl_batch_fn)(void* user, size_t m, const uint64_t* key_id, const i
                            int64_t* retry_after_ns, int64_t* reset_at_ns);
 /* Reset(ctx, key) for the test seam's host backend (rl_reset's signature) */
 typedef int (*rl_reset_fn)(void* user, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns);
+/* rl_reset_batch's signature: m resets, per-request status (RL_RESET_DONE / RL_INVALID; never null here) */
+typedef int (*rl_reset_batch_fn)(void* user, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                 const uint32_t* cfg_id, uint8_t* status);
 /* table counts / GC for the host backend (rl_table_info_get / rl_table_gc) */
 typedef int (*rl_info_fn)(void* user, int64_t now_ms, rl_table_info* out);
 typedef int (*rl_gc_fn)(void* user, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
@@ -131,6 +136,8 @@ typedef struct rl_coalescer_backend {
     void* user;
     rl_batch_fn peek;        /* rl_peek_batch: must leave the backend's state unchanged (a caller compiled
                                 before this field passes the shorter struct_size: no peek) */
+    rl_reset_batch_fn reset_batch; /* nullable (and absent from a shorter struct): resets then go through
+                                      `reset`, one call per key; its RL_EINVAL is that request's RL_INVALID */
 } rl_coalescer_backend;
 
 /* Coalescer over a GPU engine, on the device current on the calling thread
@@ -187,6 +194,17 @@ int rl_coalescer_decide_deadline(rl_coalescer* c, uint64_t key_id, int64_t ts_ns
  * request submitted after it.  Blocks until applied.  The DEL is enqueued on
  * the engine's replay stream like a batch: the pipeline is not drained. */
 int rl_coalescer_reset(rl_coalescer* c, uint64_t key_id, int64_t ts_ns, uint32_t cfg_id);
+/* m resets (rl_reset_batch_device) as one submission in sequence order; blocks
+ * until applied.  `status` (nullable): RL_RESET_DONE, or RL_INVALID for an
+ * unknown config or the reserved key -- the rest is applied and the call
+ * returns RL_OK.  One larger than max_batch is split across launches.  The
+ * submitter merges a run of adjacent reset submissions at the head of the
+ * queue -- these and single rl_coalescer_reset calls alike -- into one launch
+ * of up to max_batch; a single reset that was invalid still returns RL_EINVAL
+ * to its own caller only.  Resets count toward neither submitted / decided nor
+ * the automatic GC's insert budgets (stats.resets, stats.reset_launches). */
+int rl_coalescer_reset_batch(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                             const uint32_t* cfg_id, uint8_t* status);
 /* Read-only queries (rl_peek_batch_device, include/rl_engine.h): for each
  * request the Result AllowN would return, against the state left by every
  * request submitted before the call and none submitted after it; nothing is

@@ -158,6 +158,32 @@ int rl_reset(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns);
  * stream) waits for it. */
 int rl_reset_device(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns, void* stream);
 
+/* Many resets in one launch.  A batch of m resets (key_id[i], ts_ns[i],
+ * cfg_id[i]) has the effect of m rl_reset calls in any order (the deletes are
+ * idempotent and commute, so duplicates are fine).  A request with an unknown
+ * cfg_id or RL_KEY_RESERVED is not executed: its status is RL_INVALID, the
+ * rest of the batch is applied and the call still returns RL_OK, as a decide
+ * batch does for invalid requests.  Executed requests get RL_RESET_DONE.
+ * `status` is nullable.  rl_stats.batches / .decisions and the sticky status
+ * of rl_engine_sync are untouched.  m == 0 is RL_OK without a launch; null
+ * input arrays with m > 0 are RL_EINVAL.
+ * Host arrays; synchronous; m may exceed max_batch (staged in chunks). */
+#define RL_RESET_DONE 1
+int rl_reset_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                   const uint32_t* cfg_id, uint8_t* status);
+/* Same, with device pointers, ordered as rl_reset_device: one kernel on the
+ * engine's replay stream, after every batch enqueued before the call and
+ * before every batch enqueued after it, nothing drained; `stream` (a
+ * hipStream_t, NULL = the engine's stream) waits for it.  Without
+ * RL_OPT_PIPELINE the kernel first waits for the work queued on `stream` (the
+ * inputs); with it the inputs are complete at call time.  m may exceed
+ * max_batch. */
+int rl_reset_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                          const uint32_t* cfg_id, uint8_t* status, void* stream);
+/* resets one rl_reset_batch launch covers with one reset per thread (grid cap
+ * x block size); a larger batch strides */
+int rl_reset_grid_cap(void);
+
 /* Peek: read-only quota queries.  For each request, the outputs
  * rl_decide_batch would give for it at (ts_ns, server_ms) against the state
  * left by every batch enqueued before the call -- and nothing changes: no key

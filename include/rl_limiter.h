@@ -115,6 +115,12 @@ int rll_add_logging(rll_limiter* l, size_t capacity);
 int rll_log_drain(rll_limiter* l, char* buf, size_t len, uint64_t* dropped);
 
 int rll_reset(rll_limiter* l, const char* key, size_t keylen, int64_t now_ns, char* err, size_t errlen);
+/* ResetMany: observably m rll_reset calls in order (a key string never seen
+ * is interned as rll_reset interns it; a closed limiter fails with the same
+ * text and interns nothing), as one rl_reset_batch underneath.  RLL_OK, or
+ * RLL_ERR_RESET with the message of the failure. */
+int rll_reset_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens, int64_t now_ns,
+                   char* err, size_t errlen);
 int rll_close(rll_limiter* l);   /* Close(): later calls take the storage-error path */
 int rll_free(rll_limiter* l);
 
