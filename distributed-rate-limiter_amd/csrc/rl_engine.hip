@@ -1380,6 +1380,58 @@ static int run_reset_batch(rl_engine* e, size_t m, const uint64_t* key, const in
     return RL_OK;
 }
 
+// enqueue the peek or the reset step of the routed path (include/rl_route.h):
+// k_peek_routed / k_reset_routed on `chain`, ordered there like run_peek and
+// run_reset_batch -- after the replay of every decide batch and the DEL of
+// every reset enqueued before, before those enqueued after.  The kernel always
+// waits for s: the merge produced count, order and the store clocks there
+// (RL_OPT_PIPELINE promises the caller's arrays, not the router's).  Its end
+// is recorded into `done` when given, else so waits for it.  No buffer set is
+// taken, so m_max is not bounded by max_batch; nothing is counted in rl_stats;
+// the one flag it can raise is EF_ROUTED_OVER.
+static int run_routed_op(rl_engine* e, bool reset, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
+                         hipEvent_t done) {
+    hipStream_t c = e->chain;
+    HIPCHK(e, hipEventRecord(e->ev_in, s));
+    HIPCHK(e, hipStreamWaitEvent(c, e->ev_in, 0));
+    const uint32_t ncfg = (uint32_t)e->h_cfg.size();
+    if (reset) {
+        const int grid = (int)std::min<size_t>((m_max + RESET_BLOCK - 1) / RESET_BLOCK, (size_t)RESET_GRID);
+        k_reset_routed<<<grid, RESET_BLOCK, 0, c>>>((uint64_t)m_max, io, e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1,
+                                                    e->d_win, e->win_cap - 1, e->spill());
+    } else {
+        const int grid = (int)std::min<size_t>((m_max + PEEK_BLOCK - 1) / PEEK_BLOCK, (size_t)PEEK_GRID);
+        k_peek_routed<<<grid, PEEK_BLOCK, 0, c>>>((uint64_t)m_max, io, e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1,
+                                                  e->d_win, e->win_cap - 1, e->spill(), e->profile);
+    }
+    HIPCHK(e, hipGetLastError());
+    if (done) {
+        HIPCHK(e, hipEventRecord(done, c));
+    } else {
+        const hipEvent_t ev = reset ? e->ev_reset : e->ev_peek;
+        HIPCHK(e, hipEventRecord(ev, c));
+        HIPCHK(e, hipStreamWaitEvent(so, ev, 0));
+    }
+    return RL_OK;
+}
+
+// the C-ABI of both routed steps: argument checks as rl_decide_routed_device_io
+// / _ev, except that m_max is bounded by the 32-bit `order` only
+static int routed_op_entry(rl_engine* e, bool reset, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                           const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
+                           void* out_stream, void* done_event) {
+    if (!e || !count || (m_max && (!recv || !order || !server_ms || !res))) return RL_EINVAL;
+    if (m_max > (size_t)UINT32_MAX) return fail(e, RL_EINVAL, "routed batch bound above the 32-bit order index");
+    (void)hipSetDevice(e->device);
+    hipStream_t s = in_stream ? (hipStream_t)in_stream : e->stream;
+    if (!m_max) {   // nothing to run: the event marks the caller's stream
+        if (done_event) HIPCHK(e, hipEventRecord((hipEvent_t)done_event, s));
+        return RL_OK;
+    }
+    const RoutedIo io{recv, order, count, server_ms, res, e->d_eflags};
+    return run_routed_op(e, reset, m_max, io, s, out_stream ? (hipStream_t)out_stream : s, (hipEvent_t)done_event);
+}
+
 // Launch every kernel once at creation, on batches of requests that are all
 // rejected (no config is registered yet), so no table entry is touched: HIP
 // loads kernels lazily, and a server's first batch on either path (k_small, or
@@ -1419,6 +1471,13 @@ static int warm_up(rl_engine* e) {
         // (mb <= up_max unless RL_UP_MAX says otherwise): zero-sized launches
         k_unpermute_routed<<<1, 256, GROUP_LDS, s>>>(nullptr, nullptr, 0u, e->invalid_key, e->d_cfg, ar, ri);
         k_unpermute<<<1, 256, GROUP_LDS, s>>>(nullptr, nullptr, 0u, e->invalid_key, e->d_cfg, a, a);
+        // the routed peek and reset steps, on the same empty batch: they read
+        // the zero count and nothing else
+        const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
+        for (const bool reset : {false, true}) {
+            const int rr = run_routed_op(e, reset, 1, io, s, s, nullptr);
+            if (rr != RL_OK) return rr;
+        }
     }
     {   // the read-only query kernel
         const int r = run_peek(e, 1, a, s, false);
@@ -1525,6 +1584,18 @@ extern "C" int rl_decide_routed_device(rl_engine* e, size_t m_max, const uint32_
                                        const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
                                        void* stream) {
     return rl_decide_routed_device_io(e, m_max, count, recv, order, server_ms, res, stream, stream);
+}
+
+extern "C" int rl_peek_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                                     const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
+                                     void* in_stream, void* out_stream, void* done_event) {
+    return routed_op_entry(e, false, m_max, count, recv, order, server_ms, res, in_stream, out_stream, done_event);
+}
+
+extern "C" int rl_reset_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                                      const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
+                                      void* in_stream, void* out_stream, void* done_event) {
+    return routed_op_entry(e, true, m_max, count, recv, order, server_ms, res, in_stream, out_stream, done_event);
 }
 
 extern "C" int rl_decide_batch_keys_device(rl_engine* e, size_t m, const uint8_t* key_bytes, uint64_t nbytes,

@@ -21,6 +21,7 @@
 #pragma once
 
 #include "rl_replay.h"
+#include "rl_routed.h"
 #include "rl_semantics.h"
 #include "rl_table.h"
 #include "rl_window.h"
@@ -113,25 +114,47 @@ __device__ inline Out peek_sw(const WinState& w, const Spill& S, int64_t t, int6
     return o;
 }
 
-// One request per thread, grid-stride, in the caller's order.  The tables are
-// only read: a key a later batch's grouping is inserting right now (k_probe's
-// CAS, RL_OPT_PIPELINE) reads either as an empty slot or as a key whose entry
+// One request per thread, grid-stride.  The tables are only read: a key a
+// later batch's grouping is inserting right now (k_probe's CAS,
+// RL_OPT_PIPELINE) reads either as an empty slot or as a key whose entry
 // still holds the initial, absent state -- both are the key without state,
 // which is what it is until that batch's replay runs, after this kernel.
-__global__ __launch_bounds__(PEEK_BLOCK) void k_peek(uint64_t m, ReqArgs a, const CfgDev* __restrict__ cfgs,
-                                                     uint32_t ncfg, const TbEntry* tb, uint64_t tb_mask,
-                                                     const WinEntry* win, uint64_t win_mask, Spill spill,
-                                                     int32_t profile) {
+//
+// RT selects the input form only; the per-request logic below it is the one
+// text for both kernels.  RT = false (k_peek): m requests as arrays in the
+// caller's order (ReqArgs), results to its arrays.  RT = true (k_peek_routed):
+// the merged batch of a routed step (rl_routed.h) -- at most m requests, the
+// size in device memory; request p is rec[order[p]] with store clock sms[p],
+// or the RL_ORDER_IDENTITY form; its result is one rl_route_res at its receive
+// index (no tokens field, as the routed decide).
+template <bool RT>
+__device__ __forceinline__ void peek_requests(uint64_t m, const ReqArgs& a, const RoutedIo& io,
+                                              const CfgDev* __restrict__ cfgs, uint32_t ncfg, const TbEntry* tb,
+                                              uint64_t tb_mask, const WinEntry* win, uint64_t win_mask,
+                                              const Spill& spill, int32_t profile) {
+    RoutedForm f{};
+    if (RT) {
+        f = routed_open(m, io);
+        m = f.m;
+    }
     for (uint64_t i = blockIdx.x * (uint64_t)PEEK_BLOCK + threadIdx.x; i < m; i += (uint64_t)gridDim.x * PEEK_BLOCK) {
-        const uint64_t k = a.key[i];
-        const uint32_t c = a.cfg[i];
-        const int64_t n = a.n[i];
-        const int64_t t = a.ts[i];
+        uint64_t k;
+        uint32_t c, at = 0;
+        int64_t n, t, rsms = 0;
+        if (RT) {
+            const rl_route_rec q = routed_request(io, f, i, at, rsms);
+            k = q.key; c = q.cfg; n = q.n; t = q.ts;
+        } else {
+            k = a.key[i];
+            c = a.cfg[i];
+            n = a.n[i];
+            t = a.ts[i];
+        }
         Out o;
         if (!(c < ncfg && n >= 0 && k != EMPTY_KEY)) {
             o.decision = DEC_INVALID; o.remaining = 0; o.retry = 0; o.reset_at = 0; o.tokens = 0.0;
         } else {
-            const int64_t sms = a.sms ? a.sms[i] : floor_div(t, 1000000LL);
+            const int64_t sms = RT ? rsms : a.sms ? a.sms[i] : floor_div(t, 1000000LL);
             const CfgDev C = cfgs[c];
             if (C.alg == ALG_TOKEN_BUCKET) {
                 const uint32_t s = probe_find(tb, tb_mask, k);
@@ -157,12 +180,34 @@ __global__ __launch_bounds__(PEEK_BLOCK) void k_peek(uint64_t m, ReqArgs a, cons
                                               : peek_sw(w, spill, t, n, sms, C, profile);
             }
         }
-        a.dec[i] = o.decision;
-        a.rem[i] = o.remaining;
-        a.retry[i] = o.retry;
-        a.reset[i] = o.reset_at;
-        if (a.tok) a.tok[i] = o.tokens;
+        if (RT) {
+            routed_result(io, at, (int64_t)o.decision, o.remaining, o.retry, o.reset_at);
+        } else {
+            a.dec[i] = o.decision;
+            a.rem[i] = o.remaining;
+            a.retry[i] = o.retry;
+            a.reset[i] = o.reset_at;
+            if (a.tok) a.tok[i] = o.tokens;
+        }
     }
+}
+
+__global__ __launch_bounds__(PEEK_BLOCK) void k_peek(uint64_t m, ReqArgs a, const CfgDev* __restrict__ cfgs,
+                                                     uint32_t ncfg, const TbEntry* tb, uint64_t tb_mask,
+                                                     const WinEntry* win, uint64_t win_mask, Spill spill,
+                                                     int32_t profile) {
+    peek_requests<false>(m, a, RoutedIo{}, cfgs, ncfg, tb, tb_mask, win, win_mask, spill, profile);
+}
+
+// The peek step of the routed path (rl_peek_routed_device): the grid is sized
+// for m_max, min(ceil(m_max / PEEK_BLOCK), PEEK_GRID) blocks, since the host
+// does not know the count.  Its one atomic is the atomicOr that reports a
+// count above m_max; like k_peek it stores nothing to table memory.
+__global__ __launch_bounds__(PEEK_BLOCK) void k_peek_routed(uint64_t m_max, RoutedIo io,
+                                                            const CfgDev* __restrict__ cfgs, uint32_t ncfg,
+                                                            const TbEntry* tb, uint64_t tb_mask, const WinEntry* win,
+                                                            uint64_t win_mask, Spill spill, int32_t profile) {
+    peek_requests<true>(m_max, ReqArgs{}, io, cfgs, ncfg, tb, tb_mask, win, win_mask, spill, profile);
 }
 
 }  // namespace rl

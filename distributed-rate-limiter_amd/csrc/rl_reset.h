@@ -21,6 +21,7 @@
 // MAX_PROBES or the table mask (probe_find, spill_lookup).
 #pragma once
 
+#include "rl_routed.h"
 #include "rl_table.h"
 #include "rl_window.h"
 
@@ -38,18 +39,41 @@ constexpr uint8_t RESET_DONE = 1, RESET_INVALID = 3;
 // RL_OPT_PIPELINE) reads either as an empty slot or as a key whose entry holds
 // the initial, absent state: nothing to delete in both cases, which is the key
 // until that batch's replay runs, after this kernel.
-__global__ __launch_bounds__(RESET_BLOCK) void k_reset_batch(uint64_t m, const uint64_t* __restrict__ key,
-                                                             const int64_t* __restrict__ ts,
-                                                             const uint32_t* __restrict__ cfg,
-                                                             uint8_t* __restrict__ status,
-                                                             const CfgDev* __restrict__ cfgs, uint32_t ncfg,
-                                                             TbEntry* tb, uint64_t tb_mask, WinEntry* win,
-                                                             uint64_t win_mask, Spill spill) {
+//
+// RT selects the input form only; the delete below it is the one text for
+// both kernels.  RT = false (k_reset_batch): m resets as arrays in the caller's
+// order, a status byte each.  RT = true (k_reset_routed): the merged batch of
+// a routed step (rl_routed.h) -- at most m requests, the size in device
+// memory; the record's n and its store clock are not used (a DEL has no
+// expiry), and the status goes out as one rl_route_res {status, 0, 0, 0} at
+// the receive index.
+template <bool RT>
+__device__ __forceinline__ void reset_requests(uint64_t m, const uint64_t* __restrict__ key,
+                                               const int64_t* __restrict__ ts, const uint32_t* __restrict__ cfg,
+                                               uint8_t* __restrict__ status, const RoutedIo& io,
+                                               const CfgDev* __restrict__ cfgs, uint32_t ncfg, TbEntry* tb,
+                                               uint64_t tb_mask, WinEntry* win, uint64_t win_mask,
+                                               const Spill& spill) {
+    RoutedForm f{};
+    if (RT) {
+        f = routed_open(m, io);
+        m = f.m;
+    }
     for (uint64_t i = blockIdx.x * (uint64_t)RESET_BLOCK + threadIdx.x; i < m; i += (uint64_t)gridDim.x * RESET_BLOCK) {
-        const uint64_t k = key[i];
-        const uint32_t c = cfg[i];
+        uint64_t k;
+        uint32_t c, at = 0;
+        int64_t t = 0;   // the arrays' ts[i] is read below, only where a window start is needed
+        if (RT) {
+            int64_t sms;   // not used: a DEL does not look at the clock
+            const rl_route_rec q = routed_request(io, f, i, at, sms);
+            k = q.key; c = q.cfg; t = q.ts;
+        } else {
+            k = key[i];
+            c = cfg[i];
+        }
         if (!(c < ncfg && k != EMPTY_KEY)) {
-            if (status) status[i] = RESET_INVALID;
+            if (RT) routed_result(io, at, RESET_INVALID, 0, 0, 0);
+            else if (status) status[i] = RESET_INVALID;
             continue;
         }
         const CfgDev C = cfgs[c];
@@ -59,13 +83,36 @@ __global__ __launch_bounds__(RESET_BLOCK) void k_reset_batch(uint64_t m, const u
         } else {
             const uint32_t s = probe_find(win, win_mask, k);
             if (s != NO_SLOT) {
-                const int64_t ws = window_start(ts[i], C);
+                const int64_t ws = window_start(RT ? t : ts[i], C);
                 wk_delete(&win[s], spill, ws);
                 if (C.alg == ALG_SLIDING_WINDOW) wk_delete(&win[s], spill, ws - C.ttl_c);
             }
         }
-        if (status) status[i] = RESET_DONE;
+        if (RT) routed_result(io, at, RESET_DONE, 0, 0, 0);
+        else if (status) status[i] = RESET_DONE;
     }
+}
+
+__global__ __launch_bounds__(RESET_BLOCK) void k_reset_batch(uint64_t m, const uint64_t* __restrict__ key,
+                                                             const int64_t* __restrict__ ts,
+                                                             const uint32_t* __restrict__ cfg,
+                                                             uint8_t* __restrict__ status,
+                                                             const CfgDev* __restrict__ cfgs, uint32_t ncfg,
+                                                             TbEntry* tb, uint64_t tb_mask, WinEntry* win,
+                                                             uint64_t win_mask, Spill spill) {
+    reset_requests<false>(m, key, ts, cfg, status, RoutedIo{}, cfgs, ncfg, tb, tb_mask, win, win_mask, spill);
+}
+
+// The reset step of the routed path (rl_reset_routed_device): the grid is
+// sized for m_max, min(ceil(m_max / RESET_BLOCK), RESET_GRID) blocks, since the
+// host does not know the count.  Its one atomic is the atomicOr that reports a
+// count above m_max; its one table store is `when = ABSENT`, as k_reset_batch's.
+__global__ __launch_bounds__(RESET_BLOCK) void k_reset_routed(uint64_t m_max, RoutedIo io,
+                                                              const CfgDev* __restrict__ cfgs, uint32_t ncfg,
+                                                              TbEntry* tb, uint64_t tb_mask, WinEntry* win,
+                                                              uint64_t win_mask, Spill spill) {
+    reset_requests<true>(m_max, nullptr, nullptr, nullptr, nullptr, io, cfgs, ncfg, tb, tb_mask, win, win_mask,
+                         spill);
 }
 
 }  // namespace rl

@@ -236,6 +236,8 @@ _sig = {
     "rl_decide_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 6),
     "rl_decide_routed_device_io": (C.c_int, [vp, C.c_size_t] + [vp] * 7),
     "rl_decide_routed_device_ev": (C.c_int, [vp, C.c_size_t] + [vp] * 7),
+    "rl_peek_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
+    "rl_reset_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)
@@ -350,6 +352,42 @@ class Engine:
         rc = lib.rl_decide_routed_device_ev(self.h, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, event_p)
         if rc != RL_OK:
             raise EngineError(rc, self.last_error())
+
+    def _routed_op(self, fn, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, out_stream, event_p):
+        rc = fn(self.h, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, out_stream, event_p)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def peek_routed(self, m_max, count_p, recv_p, order_p, sms_p, res_p, stream=None, out_stream=None):
+        """rl_peek_routed_device (include/rl_route.h): the peek step of the
+        routed path on the merged batch -- what decide_routed would write,
+        with nothing changed; the kernel waits for `stream`, `out_stream`
+        (default: `stream`) waits for the results"""
+        self._routed_op(lib.rl_peek_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream,
+                        out_stream, None)
+
+    def peek_routed_ev(self, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, event_p):
+        """the same with the results' completion recorded into the hipEvent_t
+        at event_p"""
+        if not event_p:
+            raise ValueError("peek_routed_ev needs an event")
+        self._routed_op(lib.rl_peek_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, None,
+                        event_p)
+
+    def reset_routed(self, m_max, count_p, recv_p, order_p, sms_p, res_p, stream=None, out_stream=None):
+        """rl_reset_routed_device: the reset step of the routed path -- every
+        request of the merged batch deletes its key (as reset()); result
+        records {RESET_DONE or INVALID, 0, 0, 0}"""
+        self._routed_op(lib.rl_reset_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream,
+                        out_stream, None)
+
+    def reset_routed_ev(self, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, event_p):
+        """the same with the results' completion recorded into the hipEvent_t
+        at event_p"""
+        if not event_p:
+            raise ValueError("reset_routed_ev needs an event")
+        self._routed_op(lib.rl_reset_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, None,
+                        event_p)
 
     def decide_device(self, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, rem_p, retry_p, reset_p, tok_p,
                       stream=None):

@@ -53,6 +53,10 @@ def owner_of(key: np.ndarray, world: int) -> np.ndarray:
 
 INFO = 4   # RL_ROUTE_INFO
 
+# the kind of a routed step (every rank runs a step with the same kind)
+OP_DECIDE, OP_PEEK, OP_RESET = 0, 1, 2
+_OP_NAMES = {OP_DECIDE: "decide", OP_PEEK: "peek", OP_RESET: "reset"}
+
 
 def _ctx(stream):
     import contextlib
@@ -109,10 +113,21 @@ class RoutedPipeline:
     the results.
     exchange: run the collectives (world > 1 always; at world 1 they are
     loopback copies over a one-rank group, e.g. to exercise RCCL; without them
-    the buckets and results are read in place)."""
+    the buckets and results are read in place).
+
+    Step kinds (include/rl_route.h): step(..., op=OP_PEEK) asks what a decide
+    step would answer and changes nothing; step(..., op=OP_RESET) deletes the
+    requests' keys (n may be None).  Such a step is packed, exchanged, merged
+    and unpacked exactly as a decide step -- same buffer sets, collectives,
+    collective order and lookahead -- and only the owner's engine call differs:
+    peek / reset (the signature of decide: rl_peek_routed_device /
+    rl_reset_routed_device with out_stream) or peek_ev / reset_ev (that of
+    decide_ev).  Every rank must give a step the same kind.  The engine orders
+    the step after every step issued before it and before every later one."""
 
     def __init__(self, ops, decide, world, max_batch, device, pg_req=None, pg_res=None, depth=4, exchange=None,
-                 staged=False, lookahead=None, ordered=True, decide_ev=None):
+                 staged=False, lookahead=None, ordered=True, decide_ev=None, *, peek=None, peek_ev=None, reset=None,
+                 reset_ev=None):
         self.ops, self.decide, self.world = ops, decide, world
         self.dev = torch.device(device)
         self.cuda = self.dev.type == "cuda"
@@ -146,6 +161,15 @@ class RoutedPipeline:
         # behind this step's engine before the result exchanges issued in
         # between, and serialize the engine's steps
         self.decide_ev = decide_ev if self.cuda else None
+        # per step kind: (call with out_stream, call with event); a peek or
+        # reset step takes the event form when it is given, like the decide
+        self._calls = {
+            OP_DECIDE: (decide, self.decide_ev),
+            OP_PEEK: (peek, peek_ev if self.cuda else None),
+            OP_RESET: (reset, reset_ev if self.cuda else None),
+        }
+        with_events = any(ev is not None for _, ev in self._calls.values())
+        self._zero_n = None           # n of a reset step given without one
         self.slots = []
         for _ in range(depth):
             s = dict(
@@ -163,7 +187,7 @@ class RoutedPipeline:
                 ev_done=None,
                 ev_res=None,
             )
-            if self.decide_ev is not None:
+            if with_events:
                 s["ev_res"] = torch.cuda.Event()
                 s["ev_res"].record(self.R)    # materialize the event: the engine records it from now on
             self.slots.append(s)
@@ -180,7 +204,7 @@ class RoutedPipeline:
         if depth <= self.lookahead:
             raise ValueError("depth must exceed lookahead (a buffer set is reused after its step unpacked)")
         self.ordered = bool(ordered)  # False: no cross-group waits (A/B only: the order is then unconstrained)
-        self._pend = []               # (b, slot, m, dec, rem, retry, reset): result side not issued yet
+        self._pend = []               # (b, slot, m, dec, rem, retry, reset, by event): result side not issued yet
         self._ev_req = None           # after the last request-side collective issued (stream R)
         self._ev_res = None           # after the last result-side collective issued (stream U)
         # ("req" | "res", step): the collective issue order, the last 4096 (tests)
@@ -214,16 +238,30 @@ class RoutedPipeline:
         ev.record(stream)
         return ev
 
-    def step(self, b, key, ts, n, cfg, dec, rem, retry, reset):
+    def step(self, b, key, ts, n, cfg, dec, rem, retry, reset, op=OP_DECIDE):
         """route and decide batch b (device tensors: key/ts/n int64, cfg int32,
         complete now); its results reach dec/rem/retry/reset (the caller's
         order) once its result side is issued -- at once without the
         exchange, else `lookahead` steps later or at flush().  Returns the
         [(b', stream)] whose result sides this call issued: b' is complete on
-        `stream`."""
+        `stream`.  op: the step's kind, the same on every rank (OP_PEEK: the
+        answers with nothing changed; OP_RESET: the keys deleted, n ignored
+        and may be None)."""
+        if op not in self._calls:
+            raise ValueError(f"RoutedPipeline: unknown step kind {op!r}")
+        call, call_ev = self._calls[op]
+        if call is None and call_ev is None:
+            raise ValueError(f"RoutedPipeline: a {_OP_NAMES[op]} step needs the pipeline built with "
+                             f"{_OP_NAMES[op]}= or {_OP_NAMES[op]}_ev=")
         s = self.slots[b % self.depth]
         m = key.numel()
         assert m <= self.max_batch
+        if n is None:
+            if op != OP_RESET:
+                raise ValueError("RoutedPipeline: only a reset step may leave n out")
+            if self._zero_n is None:
+                self._zero_n = torch.zeros(self.max_batch, dtype=torch.int64, device=self.dev)
+            n = self._zero_n[:m]
         p, sp = self._p, self._sp
         R = self.R
         recv = s["recv"] if self.exchange else s["send"]
@@ -241,22 +279,22 @@ class RoutedPipeline:
                 self._ev_req = self._record(R)
             self.ops.merge(p(recv), p(rcnt), p(s["order"]), p(s["sms"]), p(s["count"]), sp(R))
             # the engine's grouping waits for R; U waits for its results
-            if self.decide_ev is not None:
-                self.decide_ev(self.m_max, p(s["count"]), p(recv), p(s["order"]), p(s["sms"]), p(s["res"]), sp(R),
-                               s["ev_res"].cuda_event)
+            if call_ev is not None:
+                call_ev(self.m_max, p(s["count"]), p(recv), p(s["order"]), p(s["sms"]), p(s["res"]), sp(R),
+                        s["ev_res"].cuda_event)
             else:
-                self.decide(self.m_max, p(s["count"]), p(recv), p(s["order"]), p(s["sms"]), p(s["res"]), sp(R),
-                            sp(self.U))
-        self._pend.append((b, s, m, dec, rem, retry, reset))
+                call(self.m_max, p(s["count"]), p(recv), p(s["order"]), p(s["sms"]), p(s["res"]), sp(R),
+                     sp(self.U))
+        self._pend.append((b, s, m, dec, rem, retry, reset, call_ev is not None))
         done = []
         while len(self._pend) > self.lookahead:
             done.append(self._result_side(*self._pend.pop(0)))
         return done
 
-    def _result_side(self, b, s, m, dec, rem, retry, reset):
+    def _result_side(self, b, s, m, dec, rem, retry, reset, by_event):
         p, sp, U = self._p, self._sp, self.U
         with _ctx(U):
-            if self.decide_ev is not None:
+            if by_event:
                 U.wait_event(s["ev_res"])        # this step's results (recorded by the engine)
             if self.exchange:
                 if self._ev_req is not None and self.ordered and self.pg_res is not self.pg_req:
@@ -278,11 +316,13 @@ class RoutedPipeline:
             done.append(self._result_side(*self._pend.pop(0)))
         return done
 
-    def run(self, batches, outs, done=None):
+    def run(self, batches, outs, done=None, kinds=None):
         """all batches through the pipeline: batches[b] = (key, ts, n, cfg),
-        outs[b] = (dec, rem, retry, reset); `done(b, stream)` after each"""
+        outs[b] = (dec, rem, retry, reset); `done(b, stream)` after each;
+        kinds[b] (default: every step decides) is step b's kind"""
         for b in range(len(batches)):
-            for bd, S in self.step(b, *batches[b], *outs[b]):
+            op = OP_DECIDE if kinds is None else kinds[b]
+            for bd, S in self.step(b, *batches[b], *outs[b], op=op):
                 if done is not None:
                     done(bd, S)
         for bd, S in self.flush():

@@ -39,6 +39,8 @@
  *            rl_decide_routed_device: the owner's engine reads the received
  *                               records in that order and writes 32-byte
  *                               result records at their receive index
+ *            (a peek or reset step calls rl_peek_routed_device /
+ *                               rl_reset_routed_device here instead; see there)
  *            equal-split all-to-all of the result buckets back
  *   sender   rl_route_unpack    results to the caller's order
  *
@@ -166,6 +168,45 @@ int rl_decide_routed_device_io(rl_engine* e, size_t m_max, const uint32_t* count
 int rl_decide_routed_device_ev(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
                                const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
                                void* done_event);
+
+/* Peek and Reset steps.  A routed step is homogeneous: every rank runs it with
+ * one kind -- decide, peek or reset.  A peek or reset step is packed,
+ * exchanged and merged exactly as a decide step; the owner then calls one of
+ * these instead of rl_decide_routed_device.  Request p is recv[order[p]] with
+ * store clock server_ms[p], p < *count (or the RL_ORDER_IDENTITY form), and its
+ * result is one rl_route_res at res[order[p]]:
+ *   peek   the four Result fields rl_peek_batch gives for (key, ts, n, cfg,
+ *          server_ms[p]): n == 0 is legal; n < 0, an unknown cfg and
+ *          RL_KEY_RESERVED give {RL_INVALID, 0, 0, 0}; a window count whose
+ *          INCRBY would overflow gives RL_ERROR with reset_at.  Nothing in the
+ *          tables changes and rl_stats does not move.
+ *   reset  the effect of rl_reset(cfg, key, ts) for every request, in any
+ *          order (they commute); n is ignored.  {RL_RESET_DONE, 0, 0, 0}, or
+ *          {RL_INVALID, 0, 0, 0} for an unknown cfg or RL_KEY_RESERVED.  A
+ *          request dropped at its sender was not applied.
+ * Order: the step sees the state left by every decide or reset step (and every
+ * other engine call) issued before it on this engine and none issued after it:
+ * one kernel on the engine's replay stream, as rl_peek_batch_device and
+ * rl_reset_batch_device.
+ * Store clock: a peek or reset step is a step of the shared store's timeline.
+ * rl_route_merge advances the store clock from its info rows whatever the
+ * owner runs afterwards, so the requests of a peek or reset step (dropped ones
+ * included) move the clock of every later step like a decide step's.
+ * The kernel waits for in_stream (NULL: the engine's stream), where the merge
+ * ran.  With done_event (a hipEvent_t the caller owns) the results' completion
+ * is recorded into it, as rl_decide_routed_device_ev (m_max == 0: recorded on
+ * in_stream); without, out_stream (NULL: in_stream) waits for the results, as
+ * rl_decide_routed_device_io.  m_max is bounded by `order` being 32-bit, not by
+ * the engine's max_batch (no batch buffer is used); recv and res are 16-byte
+ * aligned, as every device allocation is.  A device count above m_max runs
+ * only the first m_max requests and the next rl_engine_sync returns
+ * RL_EOVERFLOW -- the only sticky status these calls raise. */
+int rl_peek_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                          const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
+                          void* out_stream, void* done_event);
+int rl_reset_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                           const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
+                           void* out_stream, void* done_event);
 
 /* sender: back[world * cap] (the result buckets, send layout) -> the caller's
  * order; a dropped request gets decision RL_DROPPED and zeros */
