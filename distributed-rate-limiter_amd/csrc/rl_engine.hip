@@ -63,7 +63,8 @@ __global__ void k_init_win(WinEntry* t, uint64_t n) {
 // Table GC of the spill table, after the window table's k_rehash: every live
 // spill entry moves to the fresh spill table (strict CAS: two entries of one
 // user key may be moved at once) and is counted in its user key's new window
-// entry.  counters as k_rehash.
+// entry, which is inserted here (empty) if k_rehash dropped the old one as
+// expired.  counters as k_rehash.
 __global__ void k_spill_rehash(const SpillEntry* __restrict__ old, uint64_t n_old, SpillEntry* nu, uint64_t mask_new,
                                WinEntry* win, uint64_t win_mask, int64_t now_ms, int32_t profile,
                                unsigned long long* counters) {
@@ -73,7 +74,7 @@ __global__ void k_spill_rehash(const SpillEntry* __restrict__ old, uint64_t n_ol
         const SpillEntry x = old[i];
         if (!entry_live(x, now_ms, profile)) continue;
         live++;
-        const uint32_t w = probe_find(win, win_mask, x.key);
+        const uint32_t w = probe_insert(win, win_mask, x.key);
         uint64_t h = spill_home(x.key, mask_new);
         bool placed = false;
         for (uint64_t p = 0; w != NO_SLOT && p <= mask_new && p < MAX_PROBES; p++) {

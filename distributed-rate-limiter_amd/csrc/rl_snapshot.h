@@ -169,7 +169,8 @@ __device__ inline bool snap_take(const TbEntry& x, int64_t now_ms, int32_t profi
     return entry_live(x, now_ms, profile);
 }
 __device__ inline bool snap_take(const WinEntry& x, int64_t now_ms, int32_t profile) {
-    return entry_kept(x, now_ms, profile);
+    // also while its user key has spill entries (the import sorts out which are live)
+    return x.key != EMPTY_KEY && (x.nspill > 0 || entry_live(x, now_ms, profile));
 }
 __device__ inline bool snap_take(const SpillEntry& x, int64_t now_ms, int32_t profile) {
     return entry_live(x, now_ms, profile);
@@ -264,7 +265,7 @@ __global__ __launch_bounds__(SNAP_BLOCK) void k_snapshot_import(const E* __restr
         const E x = rec[i];
         c[SNAP_CHECK] += snap_hash(x, tag);
         const E y = snap_record(x);
-        if (!entry_kept(y, now_ms, profile)) continue;
+        if (!entry_live(y, now_ms, profile)) continue;
         c[SNAP_LIVE]++;
         const uint64_t h = mix64(y.key) & mask_new;
         bool ins = false;

@@ -138,14 +138,10 @@ __device__ inline bool entry_live(const SpillEntry& x, int64_t now_ms, int32_t p
     return x.key != EMPTY_KEY && x.when != ABSENT && key_alive(x.when, now_ms, profile);
 }
 
-// what table GC keeps: a window entry also stays while its user key has
-// spill entries (their liveness is recounted by k_spill_rehash)
-__device__ inline bool entry_kept(const TbEntry& x, int64_t now_ms, int32_t profile) {
-    return entry_live(x, now_ms, profile);
-}
-__device__ inline bool entry_kept(const WinEntry& x, int64_t now_ms, int32_t profile) {
-    return x.key != EMPTY_KEY && (x.nspill > 0 || entry_live(x, now_ms, profile));
-}
+// Table GC keeps the live entries.  A user key whose window entry has expired
+// and whose spill still holds a live window key gets a fresh entry from
+// k_spill_rehash, so an expired entry never outlives a GC because of spill
+// entries that have expired with it.
 __device__ inline void gc_copy(TbEntry& dst, const TbEntry& x) { dst = x; }
 __device__ inline void gc_copy(WinEntry& dst, const WinEntry& x) {
     WinEntry y = x;
@@ -164,7 +160,7 @@ __global__ void k_rehash(const E* __restrict__ old, uint64_t n_old, E* nu, uint6
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_old;
          i += (uint64_t)gridDim.x * blockDim.x) {
         const E x = old[i];
-        if (!entry_kept(x, now_ms, profile)) continue;
+        if (!entry_live(x, now_ms, profile)) continue;
         live++;
         const uint32_t s = probe_insert(nu, mask_new, x.key);
         if (s == NO_SLOT) { lost++; continue; }

@@ -534,6 +534,18 @@ def test_table_full_is_reported(rl):
     key = np.arange(2000, dtype=np.uint64)
     res = eng.decide(key, np.full(2000, T0), np.ones(2000, np.int64), np.full(2000, c, np.uint32), check=False)
     assert res.status == rl.RL_ENOMEM
+    # 1024 ids fit and 976 do not; the status is sticky until sync() has reported it
+    lost = res.decision == rl.INVALID
+    assert lost.sum() == 2000 - 1024 and (res.decision[~lost] == rl.ALLOWED).all()
+    assert eng.sync() == rl.RL_ENOMEM and eng.sync() == 0
+    assert eng.table_info(0).tb_used == 1024
+    # ids are rejected or accepted as whole keys: two more requests of each, the same ids lose both
+    rng = np.random.default_rng(0)
+    again = np.repeat(key, 2)[rng.permutation(4000)]
+    res = eng.decide(again, np.full(4000, T0 + 1000), np.ones(4000, np.int64), np.full(4000, c, np.uint32), check=False)
+    assert res.status == rl.RL_ENOMEM
+    assert np.array_equal(res.decision == rl.INVALID, lost[again.astype(np.int64)])
+    assert eng.sync() == rl.RL_ENOMEM and eng.sync() == 0
 
 
 def test_deterministic_repeat(rl):
