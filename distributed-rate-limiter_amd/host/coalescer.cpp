@@ -37,6 +37,7 @@ void Sub::carve(size_t m_) {
     cap_tb = cap_win = 0;
     info = rl_table_info{};
     snap = SnapArgs{};
+    tally = TallyArgs{};
     // layout by capacity, so a reused buffer keeps its arrays in place
     const size_t c = cap;
     uint8_t* p = mem.get();
@@ -108,12 +109,30 @@ public:
         M_ = M;
         return RL_OK;
     }
-    int launch(int i, Slot& s) override { return launch_on(i, s, rl_decide_batch_device); }
-    int launch_peek(int i, Slot& s) override { return launch_on(i, s, rl_peek_batch_device); }
+    int launch(int i, Slot& s) override { return launch_on(i, s, rl_decide_batch_device, tally_); }
+    int launch_peek(int i, Slot& s) override { return launch_on(i, s, rl_peek_batch_device, false); }
+    int tally_enable(uint32_t key_slots) override {
+        (void)hipSetDevice(dev_id_);
+        rl_tally_opts o{sizeof(rl_tally_opts), key_slots};
+        const int rc = rl_tally_enable(e_, &o);
+        tally_ = rc == RL_OK;
+        return rc;
+    }
+    // the tallies were enqueued on os_ behind their batches: rl_tally_read
+    // waits for the last of them -- which is behind the finish of every batch
+    // launched so far -- and copies on the engine's stream, where those
+    // finishes ran; batches submitted after this call are not launched yet
+    int tally_read(const TallyArgs& a) override {
+        (void)hipSetDevice(dev_id_);
+        return rl_tally_read(e_, a.cfg_out, a.cfg_cap, a.ncfg, a.key_out, a.key_cap, a.keys_tracked, a.info, a.clear);
+    }
     // rl_decide_batch_device / rl_peek_batch_device: one argument list
     using DeviceFn = int (*)(rl_engine*, size_t, const uint64_t*, const int64_t*, const int64_t*, const uint32_t*,
                              const int64_t*, uint8_t*, int64_t*, int64_t*, int64_t*, double*, void*);
-    int launch_on(int i, Slot& s, DeviceFn fn) {
+    // tally: count the batch on os_ behind its results, on the arrays the
+    // decide used; the slot's completion event is recorded behind the tally,
+    // so the slot is not reused before it has run
+    int launch_on(int i, Slot& s, DeviceFn fn, bool tally) {
         (void)hipSetDevice(dev_id_);   // the submitter thread
         Dev& d = dev_[i];
         Slot dv;
@@ -127,6 +146,7 @@ public:
             // with the device idle (profiles/r3d_stall_trace.json)
             s.t_h2d = steady_ns();
             int rc = fn(e_, m, s.key, s.ts, s.n, s.cfg, nullptr, s.dec, s.rem, s.retry, s.reset, nullptr, os_);
+            if (rc == RL_OK && tally) rc = rl_tally_batch_device(e_, m, s.key, s.cfg, s.n, s.dec, os_);
             if (rc != RL_OK) return rc;
             return hipEventRecord(d.ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
         }
@@ -139,6 +159,7 @@ public:
         if (!ok) return RL_EDEVICE;
         s.t_h2d = steady_ns();
         int rc = fn(e_, m, dv.key, dv.ts, dv.n, dv.cfg, nullptr, dv.dec, dv.rem, dv.retry, dv.reset, nullptr, os_);
+        if (rc == RL_OK && tally) rc = rl_tally_batch_device(e_, m, dv.key, dv.cfg, dv.n, dv.dec, os_);
         if (rc != RL_OK) return rc;
         ok = hipMemcpyAsync(s.dec, dv.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
         ok &= hipMemcpyAsync(s.rem, dv.rem, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
@@ -226,6 +247,7 @@ private:
         s.dec = q + 24 * M;
     }
     rl_engine* e_;
+    bool tally_ = false;         // tally_enable succeeded: launch() counts its batches
     std::vector<int8_t> table_;  // table_of per config id (submitter thread)
     int dev_id_ = 0;             // the engine's device: current when the coalescer is created
     // batches up to this size run zero-copy on the pinned slot (larger ones:
@@ -238,10 +260,111 @@ private:
     size_t M_ = 0;
 };
 
+// The usage tally over a host backend: k_tally's sums (csrc/rl_tally.h) one
+// request at a time -- the same per-config counters, the same key table (home
+// slot mix64(key) & mask, linear probing over min(slots, 64) slots, a slot
+// never released before a clear).  A host backend registers no configs: a
+// config id is known from the first request of it the backend decided (any
+// decision but RL_INVALID), up to MAX_ROWS ids.
+class HostTally {
+public:
+    static constexpr uint64_t PROBES = 64;
+    static constexpr uint32_t MAX_ROWS = 1u << 16;   // one request's config id sizes the rows: 3 MiB at most
+    int enable(uint32_t key_slots) {
+        if (key_slots > (1u << 24)) return RL_EINVAL;
+        uint64_t slots = 16;
+        while (slots < (key_slots ? key_slots : 65536u)) slots *= 2;
+        keys_.assign(slots, free_key());
+        return RL_OK;
+    }
+    void add(size_t m, const uint64_t* key, const uint32_t* cfg, const int64_t* n, const uint8_t* dec) {
+        info_.batches++;
+        info_.requests += m;
+        for (size_t i = 0; i < m; i++) {
+            const uint32_t c = cfg[i], d = dec[i];
+            if (c >= rows_.size()) {
+                if (d >= RL_INVALID || c >= MAX_ROWS) { info_.unknown_cfg++; continue; }
+                rows_.resize((size_t)c + 1, rl_tally_cfg{});
+            }
+            if (d > 3) { info_.bad_codes++; continue; }
+            const uint64_t u = n[i] > 0 ? (uint64_t)n[i] : 0;
+            rows_[c].count[d]++;
+            if (d <= RL_ALLOWED) rows_[c].units[d] += u;
+            if (d == RL_DENIED) denied(key[i], c, u);
+        }
+    }
+    int read(const TallyArgs& a) {
+        const size_t rows = a.cfg_out ? std::min(a.cfg_cap, rows_.size()) : 0;
+        if (rows) memcpy(a.cfg_out, rows_.data(), sizeof(rl_tally_cfg) * rows);
+        if (a.ncfg) *a.ncfg = (uint32_t)rows_.size();
+        if (a.key_out && a.key_cap) {
+            std::vector<rl_tally_key> tab;
+            for (const auto& r : keys_)
+                if (r.key_id != RL_KEY_RESERVED) tab.push_back(r);
+            const size_t want = std::min(a.key_cap, tab.size());
+            std::partial_sort(tab.begin(), tab.begin() + want, tab.end(), [](const rl_tally_key& x, const rl_tally_key& y) {
+                return x.denied != y.denied ? x.denied > y.denied : x.key_id < y.key_id;
+            });
+            memcpy(a.key_out, tab.data(), sizeof(rl_tally_key) * want);
+        }
+        if (a.keys_tracked) *a.keys_tracked = info_.keys_tracked;
+        if (a.info) {
+            if (a.info->struct_size < 8) return RL_EINVAL;
+            rl_tally_info I = info_;
+            I.key_slots = keys_.size();
+            I.struct_size = (uint32_t)std::min<size_t>(a.info->struct_size, sizeof I);   // bytes filled in
+            memcpy(a.info, &I, I.struct_size);
+        }
+        if (a.clear) {
+            // the config ids seen stay known: their rows are zero
+            std::fill(rows_.begin(), rows_.end(), rl_tally_cfg{});
+            std::fill(keys_.begin(), keys_.end(), free_key());
+            info_ = rl_tally_info{};
+        }
+        return RL_OK;
+    }
+
+private:
+    static rl_tally_key free_key() { return rl_tally_key{RL_KEY_RESERVED, 0, 0, 0, 0}; }
+    static uint64_t mix64(uint64_t x) {   // csrc/rl_table.h
+        x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL;
+        x ^= x >> 27; x *= 0x94d049bb133111ebULL;
+        x ^= x >> 31; return x;
+    }
+    void denied(uint64_t k, uint32_t c, uint64_t u) {
+        const uint64_t mask = keys_.size() - 1, probes = std::min<uint64_t>(keys_.size(), PROBES);
+        uint64_t s = mix64(k) & mask;
+        for (uint64_t p = 0; p < probes && k != RL_KEY_RESERVED; p++, s = (s + 1) & mask) {
+            rl_tally_key& r = keys_[s];
+            if (r.key_id == RL_KEY_RESERVED) {
+                r.key_id = k;
+                r.cfg_id = c;
+                info_.keys_tracked++;
+            }
+            if (r.key_id == k) {
+                r.denied++;
+                r.units_denied += u;
+                return;
+            }
+        }
+        info_.untracked_requests++;
+        info_.untracked_units += u;
+    }
+    std::vector<rl_tally_cfg> rows_;
+    std::vector<rl_tally_key> keys_;
+    rl_tally_info info_{};
+};
+
 // synchronous host functions (the CPU tests plug the oracle in here)
 class FnBackend : public Backend {
 public:
     explicit FnBackend(const rl_coalescer_backend& b) : b_(b) {}
+    int tally_enable(uint32_t key_slots) override {
+        const int rc = tally_.enable(key_slots);
+        tally_on_ = rc == RL_OK;
+        return rc;
+    }
+    int tally_read(const TallyArgs& a) override { return tally_on_ ? tally_.read(a) : RL_EINVAL; }
     int init(int nslots, size_t M, std::vector<Slot>* slots) override {
         slots->resize(nslots);
         mem_.resize(nslots);
@@ -262,7 +385,10 @@ public:
     }
     int launch(int, Slot& s) override {
         s.t_h2d = steady_ns();
-        return b_.batch(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset);
+        const int rc = b_.batch(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset);
+        // launch() and tally_read() both run on the submitter thread
+        if (rc == RL_OK && tally_on_) tally_.add(s.m, s.key, s.cfg, s.n, s.dec);
+        return rc;
     }
     int launch_reset_batch(int, Slot& s) override {
         s.t_h2d = steady_ns();
@@ -291,6 +417,8 @@ public:
 
 private:
     rl_coalescer_backend b_;
+    HostTally tally_;
+    bool tally_on_ = false;
     std::vector<std::unique_ptr<uint8_t[]>> mem_;
 };
 
@@ -318,6 +446,10 @@ Coalescer::Coalescer(std::unique_ptr<Backend> be, const rl_coalescer_opts& o) : 
 int Coalescer::start() {
     int rc = be_->init((int)o_.max_in_flight, o_.max_batch, &slots_);
     if (rc != RL_OK) return rc;
+    if (o_.tally_key_slots) {
+        rc = be_->tally_enable(o_.tally_key_slots);
+        if (rc != RL_OK) return rc;
+    }
     t_sub_ = std::thread([this] { submitter(); });
     t_done_ = std::thread([this] { completer(); });
     return RL_OK;
@@ -403,11 +535,12 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
 }
 
 int Coalescer::SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
-                        uint64_t cap_win, uint64_t* ticket, void* tag, const SnapArgs* snap) {
+                        uint64_t cap_win, uint64_t* ticket, void* tag, const SnapArgs* snap, const TallyArgs* tally) {
     Sub* s = get_sub(1);
     s->op = op;
     s->tag = tag;
     if (snap) s->snap = *snap;
+    if (tally) s->tally = *tally;
     s->key[0] = key;
     s->ts[0] = ts;
     s->n[0] = 1;
@@ -598,6 +731,9 @@ int Coalescer::run_table_op(Sub* op) {
     int st;
     if (op->op == OP_INFO) {
         st = be_->table_info(op->now_ms, &info);
+    } else if (op->op == OP_TALLY) {
+        // every batch before it is launched, its tally enqueued behind it
+        st = be_->tally_read(op->tally);
     } else if (op->op == OP_SNAPSHOT) {
         st = be_->snapshot(op->now_ms, op->snap.world, op->snap.rank, op->snap.buf, op->snap.len, op->snap.out);
     } else {
@@ -728,6 +864,7 @@ void Coalescer::submitter() {
             f->in_queue = false;
             pending_ -= 1;
             f->taken = 1;
+            const Op fop = f->op;
             lk.unlock();
             const int st = run_table_op(f);
             lk.lock();
@@ -738,8 +875,8 @@ void Coalescer::submitter() {
             if (f->waiting) f->cv.notify_all();
             notify_locked(f);
             maybe_free_locked(f);
-            // a manual GC invalidates the automatic GC's count
-            gc_counted_ = false;
+            // a manual GC invalidates the automatic GC's count (a tally read touches no table)
+            if (fop != OP_TALLY) gc_counted_ = false;
             continue;
         }
         const int si = next_slot_;
@@ -910,8 +1047,14 @@ static int create(std::unique_ptr<rlc::Backend> be, const rl_coalescer_opts* opt
     rl_coalescer_opts o{};
     o.struct_size = sizeof o;
     if (opts) {
-        if (opts->struct_size != sizeof(rl_coalescer_opts)) return RL_EINVAL;
-        o = *opts;
+        // a caller compiled before a trailing field was added passes a shorter
+        // struct: any size from the first such field's offset up to ours (what
+        // it does not cover stays 0, off)
+        if (opts->struct_size < offsetof(rl_coalescer_opts, tally_key_slots) ||
+            opts->struct_size > sizeof(rl_coalescer_opts))
+            return RL_EINVAL;
+        memcpy(&o, opts, opts->struct_size);
+        o.struct_size = sizeof o;
     }
     auto* c = new rlc::Coalescer(std::move(be), o);
     int rc = c->start();
@@ -1034,9 +1177,9 @@ extern "C" int rl_coalescer_peek(rl_coalescer* c, size_t m, const uint64_t* key_
 }
 
 static int table_op(rl_coalescer* c, rlc::Op op, int64_t now_ms, uint64_t tb, uint64_t win, rl_table_info* out,
-                    const rlc::SnapArgs* snap = nullptr) {
+                    const rlc::SnapArgs* snap = nullptr, const rlc::TallyArgs* tally = nullptr) {
     uint64_t t;
-    int rc = c->c->SubmitOp(op, 0, 0, 0, now_ms, tb, win, &t, nullptr, snap);
+    int rc = c->c->SubmitOp(op, 0, 0, 0, now_ms, tb, win, &t, nullptr, snap, tally);
     if (rc != RL_OK) return rc;
     rl_table_info info{};
     rc = c->c->Wait(t, -1, nullptr, nullptr, nullptr, nullptr, nullptr, &info);
@@ -1078,6 +1221,22 @@ extern "C" int rl_coalescer_restore(rl_coalescer* c, const void* buf, size_t len
     a.buf = const_cast<void*>(buf);
     a.len = len;
     return table_op(c, rlc::OP_RESTORE, now_ms, tb_capacity, win_capacity, out, &a);
+}
+
+extern "C" int rl_coalescer_tally(rl_coalescer* c, rl_tally_cfg* cfg_out, size_t cfg_cap, uint32_t* ncfg,
+                                  rl_tally_key* key_out, size_t key_cap, uint64_t* keys_tracked, rl_tally_info* info,
+                                  int clear) {
+    if (!c || !c->c->TallyOn() || (info && info->struct_size < 8)) return RL_EINVAL;
+    rlc::TallyArgs a;
+    a.cfg_out = cfg_out;
+    a.cfg_cap = cfg_cap;
+    a.ncfg = ncfg;
+    a.key_out = key_out;
+    a.key_cap = key_cap;
+    a.keys_tracked = keys_tracked;
+    a.info = info;
+    a.clear = clear;
+    return table_op(c, rlc::OP_TALLY, 0, 0, 0, nullptr, nullptr, &a);
 }
 
 extern "C" int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out) {

@@ -47,10 +47,28 @@ struct Slot {
     std::vector<Part> parts;
 };
 
+// OP_TALLY arguments (rl_tally_read's): the caller's buffers (it blocks until
+// the operation is done)
+struct TallyArgs {
+    rl_tally_cfg* cfg_out = nullptr;
+    size_t cfg_cap = 0;
+    uint32_t* ncfg = nullptr;
+    rl_tally_key* key_out = nullptr;
+    size_t key_cap = 0;
+    uint64_t* keys_tracked = nullptr;
+    rl_tally_info* info = nullptr;
+    int clear = 0;
+};
+
 // where batches go: the GPU engine, or synchronous host functions (tests)
 class Backend {
 public:
     virtual ~Backend() = default;
+    // usage tally (rl_coalescer_opts.tally_key_slots): once enabled, launch()
+    // counts every batch behind its decisions, before wait(slot) returns
+    virtual int tally_enable(uint32_t key_slots) = 0;
+    // rl_tally_read: every batch launched so far is counted (synchronous)
+    virtual int tally_read(const TallyArgs& a) = 0;
     virtual int init(int nslots, size_t max_batch, std::vector<Slot>* slots) = 0;
     virtual int launch(int slot, Slot& s) = 0;   // asynchronous
     // the slot's s.m resets (key, ts, cfg; rl_reset_batch_device) after every
@@ -83,7 +101,7 @@ public:
 std::unique_ptr<Backend> make_gpu_backend(rl_engine* e);
 std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b);
 
-enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE };
+enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY };
 // submissions that carry requests and results (the rest carry one operation)
 inline bool has_requests(Op op) { return op == OP_REQ || op == OP_PEEK; }
 // submissions the submitter takes from the queue in parts of up to max_batch:
@@ -124,6 +142,7 @@ struct Sub {
     uint64_t cap_tb = 0, cap_win = 0;
     rl_table_info info{};
     SnapArgs snap;
+    TallyArgs tally;              // OP_TALLY
     std::condition_variable cv;
     std::unique_ptr<uint8_t[]> mem;
     uint64_t* key;
@@ -163,7 +182,10 @@ public:
     // a single Reset (an OP_RESET submission of one) / table count / table GC /
     // snapshot / restore, queued in sequence order
     int SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
-                 uint64_t cap_win, uint64_t* ticket, void* tag = nullptr, const SnapArgs* snap = nullptr);
+                 uint64_t cap_win, uint64_t* ticket, void* tag = nullptr, const SnapArgs* snap = nullptr,
+                 const TallyArgs* tally = nullptr);
+    // rl_coalescer_opts.tally_key_slots != 0
+    bool TallyOn() const { return o_.tally_key_slots != 0; }
     // Completion callback for submissions made with a tag: fn(user, ticket,
     // tag) runs once when the submission is done (applied, failed, or dropped
     // unapplied), on a coalescer thread (or the thread of a Cancel / Wait that

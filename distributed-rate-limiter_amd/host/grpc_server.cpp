@@ -15,6 +15,7 @@
 #include <fcntl.h>
 #include <netinet/in.h>
 #include <netinet/tcp.h>
+#include <stddef.h>
 #include <string.h>
 #include <sys/epoll.h>
 #include <sys/eventfd.h>
@@ -24,6 +25,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <queue>
@@ -41,7 +43,7 @@
 namespace {
 
 constexpr int GRPC_OK = 0, GRPC_CANCELLED = 1, GRPC_INVALID_ARGUMENT = 3, GRPC_DEADLINE_EXCEEDED = 4,
-              GRPC_NOT_FOUND = 5, GRPC_UNIMPLEMENTED = 12, GRPC_INTERNAL = 13, GRPC_UNAVAILABLE = 14;
+              GRPC_NOT_FOUND = 5, GRPC_FAILED_PRECONDITION = 9, GRPC_UNIMPLEMENTED = 12, GRPC_INTERNAL = 13, GRPC_UNAVAILABLE = 14;
 const char* const ERR_INVALID_N = "invalid n: must be greater than 0";   // errors.go:16
 
 int64_t realtime_ns() {
@@ -102,6 +104,16 @@ void put_bytes(std::string& o, uint32_t field, std::string_view v) {
     put_varint(o, ((uint64_t)field << 3) | 2);
     put_varint(o, v.size());
     o.append(v.data(), v.size());
+}
+
+void put_fixed64(std::string& o, uint32_t field, uint64_t v) {   // always written
+    put_varint(o, ((uint64_t)field << 3) | 1);
+    for (int i = 0; i < 8; i++) o.push_back((char)(v >> (8 * i)));
+}
+void put_msg(std::string& o, uint32_t field, const std::string& m) {   // an embedded message, empty or not
+    put_varint(o, ((uint64_t)field << 3) | 2);
+    put_varint(o, m.size());
+    o += m;
 }
 
 // AllowRequest / AllowNRequest / ResetRequest: limiter = 1, key = 2, n = 3
@@ -211,8 +223,20 @@ struct Limiter {
 struct Io;
 struct Conn;
 
-// K_PEEK: a read-only AllowN (rl_coalescer_peek); K_RESET_BATCH: many resets, one coalescer submission
-enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH };
+// K_PEEK: a read-only AllowN (rl_coalescer_peek); K_RESET_BATCH: many resets, one coalescer submission;
+// K_USAGE: RateLimiterMetrics.Usage, one rl_coalescer_tally
+enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE };
+
+// what a Usage RPC's tally read writes into (OP_TALLY runs on the submitter
+// thread): owned by the Rpc, which stays in its loop's table until the read is
+// done even when the client has gone
+struct UsageBuf {
+    std::vector<rl_tally_cfg> rows;
+    std::vector<rl_tally_key> keys;
+    uint32_t ncfg = 0;
+    uint64_t tracked = 0;
+    rl_tally_info info{};
+};
 
 struct Stream {
     int32_t id = 0;
@@ -228,6 +252,7 @@ struct BatchItem {
     int64_t n;
     int err;                   // 0: submitted; 1: unknown limiter; 2: invalid n
     std::string name;          // the unknown limiter's name
+    std::string key;           // with the tally on: the key's name (remembered if it is denied)
 };
 
 struct Rpc {
@@ -239,6 +264,8 @@ struct Rpc {
     const Limiter* lim = nullptr;
     std::vector<BatchItem> items;
     size_t m = 0;              // requests submitted
+    std::string key;           // K_ALLOW with the tally on: the key's name
+    std::unique_ptr<UsageBuf> usage;   // K_USAGE
 };
 
 struct Server;
@@ -280,6 +307,34 @@ struct Server {
     std::vector<std::unique_ptr<Io>> ios;
     nghttp2_session_callbacks* cbs = nullptr;
     std::atomic<uint64_t> n_conn{0}, n_rpc{0}, n_dec{0}, n_err{0}, n_cancel{0};
+    // RateLimiterMetrics.Usage: on, and the names of the last names_cap keys a
+    // denied response went out for (any loop adds, a Usage response reads)
+    bool tally = false;
+    size_t names_cap = 4096;
+    std::mutex names_mu;
+    std::unordered_map<uint64_t, std::pair<std::string, uint64_t>> names;   // id -> (name, stamp)
+    std::deque<std::pair<uint64_t, uint64_t>> names_order;                  // (id, stamp), oldest first
+    uint64_t names_stamp = 0;
+    void remember(const Limiter* l, std::string_view key) {
+        if (!tally || !names_cap) return;
+        const uint64_t id = key_id(l, key);
+        std::lock_guard<std::mutex> g(names_mu);
+        const uint64_t stamp = ++names_stamp;
+        names[id] = {std::string(key), stamp};
+        names_order.push_back({id, stamp});
+        // newest wins: drop the oldest entries (a stale order record is skipped)
+        while (names.size() > names_cap || names_order.size() > 4 * names_cap + 16) {
+            const auto o = names_order.front();
+            names_order.pop_front();
+            auto it = names.find(o.first);
+            if (it != names.end() && it->second.second == o.second) names.erase(it);
+        }
+    }
+    std::string name_of(uint64_t id) {
+        std::lock_guard<std::mutex> g(names_mu);
+        auto it = names.find(id);
+        return it == names.end() ? std::string() : it->second.first;
+    }
 
     int64_t now() {
         if (!clock_step) return realtime_ns();
@@ -415,11 +470,51 @@ Outcome decide_outcome(const Limiter* lim, int64_t t, int rc, uint8_t dec, int64
 void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, const int64_t* rem,
                 const int64_t* retry, const int64_t* reset) {
     Conn* c = rpc.conn;
+    if (!c) return;                       // detached: its stream or its connection went (cb_close, close_conn)
     auto it = c->streams.find(rpc.sid);
     if (it == c->streams.end()) return;   // the client went away
     Stream* st = it->second.get();
     st->pending = false;
     std::string msg;
+    if (rpc.kind == K_USAGE) {
+        Server* s = io->srv;
+        if (rc == RL_EINVAL) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "usage tally is off");
+        if (rc != RL_OK) return respond_err(c, st, GRPC_UNAVAILABLE, "failed to read usage: engine status " + std::to_string(rc));
+        const UsageBuf& u = *rpc.usage;
+        std::string one;
+        for (const Limiter& l : s->lims) {       // UsageResponse.limiters = 1
+            one.clear();
+            put_bytes(one, 1, l.name);
+            if (l.cfg < u.ncfg && l.cfg < u.rows.size()) {
+                const rl_tally_cfg& r = u.rows[l.cfg];
+                put_int(one, 2, (int64_t)r.count[RL_ALLOWED]);
+                put_int(one, 3, (int64_t)r.count[RL_DENIED]);
+                put_int(one, 4, (int64_t)r.count[RL_ERROR]);
+                put_int(one, 5, (int64_t)r.count[RL_INVALID]);
+                put_int(one, 6, (int64_t)r.units[1]);
+                put_int(one, 7, (int64_t)r.units[0]);
+            }
+            put_msg(msg, 1, one);
+        }
+        const size_t nk = (size_t)std::min<uint64_t>(u.keys.size(), u.tracked);
+        for (size_t i = 0; i < nk; i++) {        // UsageResponse.keys = 2
+            const rl_tally_key& k = u.keys[i];
+            one.clear();
+            for (const Limiter& l : s->lims)
+                if (l.cfg == k.cfg_id) {
+                    put_bytes(one, 1, l.name);
+                    break;
+                }
+            put_fixed64(one, 2, k.key_id);
+            put_bytes(one, 3, s->name_of(k.key_id));
+            put_int(one, 4, (int64_t)k.denied);
+            put_int(one, 5, (int64_t)k.units_denied);
+            put_msg(msg, 2, one);
+        }
+        put_int(msg, 3, (int64_t)u.info.untracked_requests);
+        put_int(msg, 4, (int64_t)u.tracked);
+        return respond_ok(c, st, msg);
+    }
     if (rpc.kind == K_RESET_BATCH) {
         // ResetBatchResponse.errors = 1: one string per request, "" = done
         size_t j = 0;
@@ -443,6 +538,7 @@ void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, c
         else respond_ok(c, st, msg);
         return;
     }
+    if (rpc.kind == K_ALLOW && rc == RL_OK && dec && dec[0] == RL_DENIED) io->srv->remember(rpc.lim, rpc.key);
     if (rpc.kind == K_ALLOW || rpc.kind == K_PEEK) {
         const Outcome o = decide_outcome(rpc.lim, rpc.t, rc, dec ? dec[0] : 0, rem ? rem[0] : 0, retry ? retry[0] : 0,
                                          reset ? reset[0] : 0);
@@ -457,6 +553,7 @@ void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, c
         if (b.err == 1) r.error = "unknown limiter " + py_repr(b.name);
         else if (b.err == 2) r.error = ERR_INVALID_N;
         else {
+            if (rc == RL_OK && dec && dec[j] == RL_DENIED) io->srv->remember(b.lim, b.key);
             r = decide_outcome(b.lim, rpc.t, rc, dec ? dec[j] : 0, rem ? rem[j] : 0, retry ? retry[j] : 0,
                                reset ? reset[j] : 0).r;
             j++;
@@ -560,6 +657,44 @@ void dispatch(Conn* c, Stream* st) {
         const size_t mm = rpc.m;
         return submit_rpc(io, c, st, std::move(rpc), mm, key.data(), ts.data(), nullptr, cfg.data());
     }
+    if (p == "/ratelimiter.v1.RateLimiterMetrics/Usage") {
+        if (!s->tally || !s->co->TallyOn()) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "usage tally is off");
+        uint64_t top = 0, clear = 0;   // UsageRequest: top = 1, clear = 2
+        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
+        while (pb.more()) {
+            const uint64_t tag = pb.varint();
+            if ((tag >> 3) == 1 && (tag & 7) == 0) top = pb.varint() & 0xffffffffu;
+            else if ((tag >> 3) == 2 && (tag & 7) == 0) clear = pb.varint();
+            else pb.skip((uint32_t)(tag & 7));
+        }
+        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad UsageRequest");
+        // one table operation in the coalescer's sequence, completed through
+        // the ticket's notification: the event loop does not wait for it
+        Rpc rpc{c, st->id, K_USAGE, 0, 0, nullptr, {}, 0};
+        rpc.usage.reset(new UsageBuf());
+        UsageBuf& u = *rpc.usage;
+        uint32_t rows = 0;
+        for (const Limiter& l : s->lims) rows = std::max(rows, l.cfg + 1);
+        u.rows.assign(rows, rl_tally_cfg{});
+        u.keys.assign((size_t)std::min<uint64_t>(top, 1u << 16), rl_tally_key{});
+        u.info.struct_size = sizeof u.info;
+        rlc::TallyArgs a;
+        a.cfg_out = u.rows.data();
+        a.cfg_cap = u.rows.size();
+        a.ncfg = &u.ncfg;
+        a.key_out = u.keys.data();
+        a.key_cap = u.keys.size();
+        a.keys_tracked = &u.tracked;
+        a.info = &u.info;
+        a.clear = clear != 0;
+        uint64_t ticket = 0;
+        const int rc = s->co->SubmitOp(rlc::OP_TALLY, 0, 0, 0, 0, 0, 0, &ticket, io, nullptr, &a);
+        if (rc != RL_OK) return finish_rpc(io, 0, rpc, rc, nullptr, nullptr, nullptr, nullptr);
+        st->pending = true;
+        st->ticket = ticket;
+        io->rpcs.emplace(ticket, std::move(rpc));
+        return;
+    }
     static const std::string peek_path = "/ratelimiter.v1.RateLimiterStatus/Peek";
     const bool is_peek = p == peek_path;
     if (!is_peek && p.compare(0, svc.size(), svc) != 0) return respond_err(c, st, GRPC_UNIMPLEMENTED, "unknown service");
@@ -578,6 +713,7 @@ void dispatch(Conn* c, Stream* st) {
         const uint64_t id = s->key_id(lim, r.key);
         const size_t mm = m == "Reset" ? 0 : 1;
         Rpc rpc{c, st->id, m == "Reset" ? K_RESET : is_peek ? K_PEEK : K_ALLOW, t, 0, lim, {}, mm};
+        if (s->tally && rpc.kind == K_ALLOW) rpc.key = std::string(r.key);
         const int64_t n = r.n;
         const uint32_t cfg = lim->cfg;
         return submit_rpc(io, c, st, std::move(rpc), mm, &id, &t, &n, &cfg);
@@ -607,6 +743,7 @@ void dispatch(Conn* c, Stream* st) {
                 ts.push_back(rpc.t);
                 n.push_back(r.n);
                 cfg.push_back(it.lim->cfg);
+                if (s->tally) it.key = std::string(r.key);
             }
             rpc.items.push_back(std::move(it));
         }
@@ -674,12 +811,20 @@ int cb_close(nghttp2_session*, int32_t sid, uint32_t, void* u) {
     if (st->pending) {
         // the client reset the stream (its deadline, ctx cancel): cancel the
         // submission -- dropped unapplied if not launched -- and release it
+        // (a Usage read is left to finish: the submitter may be writing its
+        // buffers.  It is detached from the connection, which may be deleted
+        // before the read is done; collect() then only releases the ticket
+        // and the buffers)
         Io* io = c->io;
-        io->srv->co->Cancel(st->ticket);
         auto r = io->rpcs.find(st->ticket);
-        if (r != io->rpcs.end()) {
-            (void)io->srv->co->Wait(st->ticket, 0, nullptr, nullptr, nullptr, nullptr);
-            io->rpcs.erase(r);
+        if (r != io->rpcs.end() && r->second.kind == K_USAGE) {
+            r->second.conn = nullptr;
+        } else {
+            io->srv->co->Cancel(st->ticket);
+            if (r != io->rpcs.end()) {
+                (void)io->srv->co->Wait(st->ticket, 0, nullptr, nullptr, nullptr, nullptr);
+                io->rpcs.erase(r);
+            }
         }
         io->srv->n_cancel++;
     }
@@ -695,8 +840,12 @@ void close_conn(Io* io, Conn* c) {
     for (auto& kv : c->streams) {
         Stream* st = kv.second.get();
         if (!st->pending) continue;
-        io->srv->co->Cancel(st->ticket);
         auto r = io->rpcs.find(st->ticket);
+        if (r != io->rpcs.end() && r->second.kind == K_USAGE) {   // left to finish, detached: cb_close
+            r->second.conn = nullptr;
+            continue;
+        }
+        io->srv->co->Cancel(st->ticket);
         if (r != io->rpcs.end()) {
             (void)io->srv->co->Wait(st->ticket, 0, nullptr, nullptr, nullptr, nullptr);
             io->rpcs.erase(r);
@@ -882,10 +1031,12 @@ struct rl_grpc_server {
 extern "C" int rl_grpc_server_start(rl_coalescer* c, const rl_grpc_limiter* limiters, size_t n_limiters,
                                     const rl_grpc_opts* opts, rl_grpc_server** out) {
     rlc::Coalescer* co = rlc::unwrap(c);
-    if (!co || !out || (n_limiters && !limiters) || (opts && opts->struct_size != sizeof(rl_grpc_opts)))
+    // a caller compiled before a trailing field was added passes a shorter struct
+    if (!co || !out || (n_limiters && !limiters) ||
+        (opts && (opts->struct_size < offsetof(rl_grpc_opts, tally) || opts->struct_size > sizeof(rl_grpc_opts))))
         return RL_EINVAL;
     rl_grpc_opts o{};
-    if (opts) o = *opts;
+    if (opts) memcpy(&o, opts, opts->struct_size);
     const int nio = o.io_threads ? (int)o.io_threads : 4;
     if (nio > 64) return RL_EINVAL;
     auto* g = new rl_grpc_server();
@@ -894,6 +1045,8 @@ extern "C" int rl_grpc_server_start(rl_coalescer* c, const rl_grpc_limiter* limi
     s.isolate = o.isolate != 0;
     s.clock_start = o.clock_start_ns;
     s.clock_step = o.clock_step_ns;
+    s.tally = o.tally != 0;
+    if (o.names_cap) s.names_cap = o.names_cap;
     s.lims.reserve(n_limiters);
     for (size_t i = 0; i < n_limiters; i++) {
         const rl_grpc_limiter& l = limiters[i];
@@ -980,6 +1133,15 @@ extern "C" int rl_grpc_server_destroy(rl_grpc_server* g) {
     if (!g) return RL_EINVAL;
     rl_grpc_server_shutdown(g, 0);
     Server& s = g->s;
+    // a Usage read still queued or running when the loops ended writes into
+    // buffers its Rpc owns: wait for it (the loops have been joined), but not
+    // for ever -- a coalescer that no longer runs its queue never completes
+    // it -- and a read that has not ended by then keeps its buffers (leaked)
+    for (auto& io : s.ios)
+        for (auto& kv : io->rpcs)
+            if (kv.second.kind == K_USAGE &&
+                s.co->Wait(kv.first, 10LL * 1000000000LL, nullptr, nullptr, nullptr, nullptr) == RL_ETIMEOUT)
+                (void)kv.second.usage.release();
     s.co->SetNotify(nullptr, nullptr);
     for (auto& io : s.ios) {
         close(io->ep);

@@ -93,6 +93,22 @@ class rl_table_info(_Sized):
                                           "win_live", "spill_capacity", "spill_used", "spill_live")]
 
 
+class rl_tally_opts(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("key_slots", C.c_uint32)]
+
+
+class rl_tally_info(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("pad_", C.c_uint32)] + [
+        (k, C.c_uint64) for k in ("key_slots", "keys_tracked", "untracked_requests", "untracked_units",
+                                  "unknown_cfg", "bad_codes", "batches", "requests")]
+
+
+# rl_tally_cfg / rl_tally_key as numpy records
+TALLY_CFG = np.dtype([("count", np.uint64, 4), ("units", np.uint64, 2)])
+TALLY_KEY = np.dtype([("key_id", np.uint64), ("denied", np.uint64), ("units_denied", np.uint64),
+                      ("cfg_id", np.uint32), ("pad_", np.uint32)])
+
+
 class rl_snapshot_info(_Sized):
     """include/rl_snapshot.h"""
     _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("profile", C.c_int32), ("world", C.c_uint32),
@@ -112,6 +128,7 @@ class rl_coalescer_opts(_Sized):
         ("gc_margin_ms", C.c_int64),
         ("gc_max_tb_capacity", C.c_uint64),
         ("gc_max_win_capacity", C.c_uint64),
+        ("tally_key_slots", C.c_uint32),
     ]
 
 
@@ -150,6 +167,14 @@ _sig = {
     "rl_reset_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
     "rl_reset_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
     "rl_reset_grid_cap": (C.c_int, []),
+    "rl_tally_enable": (C.c_int, [vp, C.POINTER(rl_tally_opts)]),
+    "rl_tally_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
+    "rl_tally_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
+    "rl_tally_read": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), vp, C.c_size_t, C.POINTER(C.c_uint64),
+                                C.POINTER(rl_tally_info), C.c_int]),
+    "rl_tally_grid_cap": (C.c_int, []),
+    "rl_coalescer_tally": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), vp, C.c_size_t,
+                                     C.POINTER(C.c_uint64), C.POINTER(rl_tally_info), C.c_int]),
     "rl_engine_sync": (C.c_int, [vp]),
     "rl_reset": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int64]),
     "rl_reset_device": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int64, vp]),
@@ -277,6 +302,18 @@ OPT_PIPELINE = 1
 PEEK_GRID_CAP = lib.rl_peek_grid_cap()
 # the same of k_reset_batch
 RESET_GRID_CAP = lib.rl_reset_grid_cap()
+# the same of k_tally
+TALLY_GRID_CAP = lib.rl_tally_grid_cap()
+
+
+@dataclass
+class Tally:
+    """rl_tally_read: cfg[c] the counters of config c (TALLY_CFG), keys the
+    top throttled keys (TALLY_KEY, most denied first), info the rl_tally_info"""
+    cfg: np.ndarray
+    keys: np.ndarray
+    keys_tracked: int
+    info: rl_tally_info
 
 
 class Engine:
@@ -448,6 +485,47 @@ class Engine:
         rc = lib.rl_reset_batch_device(self.h, m, key_p, ts_p, cfg_p, status_p, stream)
         if rc != RL_OK:
             raise EngineError(rc, self.last_error())
+
+    def tally_enable(self, key_slots=0):
+        """rl_tally_enable: allocate the usage tally (key_slots: records of
+        the throttled-key table, 0 = 65536)"""
+        o = rl_tally_opts(key_slots=key_slots)
+        rc = lib.rl_tally_enable(self.h, C.byref(o))
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def tally(self, key, cfg, n, decision):
+        """rl_tally_batch: count one finished batch (host arrays, synchronous)"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        decision = np.ascontiguousarray(decision, dtype=np.uint8)
+        m = key.size
+        assert cfg.size == m and n.size == m and decision.size == m
+        rc = lib.rl_tally_batch(self.h, m, _ptr(key), _ptr(cfg), _ptr(n), _ptr(decision))
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def tally_device(self, m, key_p, cfg_p, n_p, dec_p, stream=None):
+        """rl_tally_batch_device: the same with device pointers, enqueued on `stream`"""
+        rc = lib.rl_tally_batch_device(self.h, m, key_p, cfg_p, n_p, dec_p, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def tally_read(self, top=0, clear=False) -> Tally:
+        """rl_tally_read: every config's counters and the `top` most denied
+        tracked keys; clear: zero everything afterwards"""
+        ncfg, tracked, info = C.c_uint32(), C.c_uint64(), rl_tally_info()
+        rc = lib.rl_tally_read(self.h, None, 0, C.byref(ncfg), None, 0, None, None, 0)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        cfg = np.zeros(ncfg.value, TALLY_CFG)
+        keys = np.zeros(top, TALLY_KEY)
+        rc = lib.rl_tally_read(self.h, _ptr(cfg), cfg.size, C.byref(ncfg), _ptr(keys), top, C.byref(tracked),
+                               C.byref(info), 1 if clear else 0)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        return Tally(cfg, keys[:min(top, tracked.value)], tracked.value, info)
 
     def stats(self) -> rl_stats:
         s = rl_stats()
@@ -873,11 +951,11 @@ class Coalescer:
 
     def __init__(self, engine, max_batch=65536, max_in_flight=3, linger_ns=0, queue_cap=0, reset=None,
                  table_info=None, gc=None, peek=None, gc_interval_ns=0, gc_high_pct=0, gc_margin_ms=0,
-                 gc_max_tb_capacity=0, gc_max_win_capacity=0, reset_batch=None):
+                 gc_max_tb_capacity=0, gc_max_win_capacity=0, reset_batch=None, tally_key_slots=0):
         o = rl_coalescer_opts(max_batch=max_batch, max_in_flight=max_in_flight, gc_high_pct=gc_high_pct,
                               linger_ns=linger_ns, queue_cap=queue_cap, gc_interval_ns=gc_interval_ns,
                               gc_margin_ms=gc_margin_ms, gc_max_tb_capacity=gc_max_tb_capacity,
-                              gc_max_win_capacity=gc_max_win_capacity)
+                              gc_max_win_capacity=gc_max_win_capacity, tally_key_slots=tally_key_slots)
         h = vp()
         if isinstance(engine, Engine):
             rc = lib.rl_coalescer_create(engine.h, C.byref(o), C.byref(h))
@@ -972,6 +1050,21 @@ class Coalescer:
         rc = lib.rl_coalescer_restore(self.h, _ptr(blob), blob.size, now_ms, tb_capacity, win_capacity, C.byref(out))
         return rc, out
 
+    def tally(self, top=0, clear=False, max_configs=1024):
+        """rl_coalescer_tally: the usage tally in sequence order -- every
+        request submitted before the call is counted, none submitted after.
+        -> (rc, Tally); tally_key_slots=0 at creation: RL_EINVAL"""
+        ncfg, tracked, info = C.c_uint32(), C.c_uint64(), rl_tally_info()
+        # one call, one point of the sequence: room for max_configs rows
+        cfg = np.zeros(max_configs, TALLY_CFG)
+        keys = np.zeros(top, TALLY_KEY)
+        rc = lib.rl_coalescer_tally(self.h, _ptr(cfg), cfg.size, C.byref(ncfg), _ptr(keys), top, C.byref(tracked),
+                                    C.byref(info), 1 if clear else 0)
+        if rc != RL_OK:
+            return rc, None
+        # rows of config ids >= max_configs are not returned (as rl_tally_read's cfg_cap)
+        return rc, Tally(cfg[:min(ncfg.value, cfg.size)], keys[:min(top, tracked.value)], tracked.value, info)
+
     def stats(self) -> rl_coalescer_stats:
         st = rl_coalescer_stats()
         lib.rl_coalescer_get_stats(self.h, C.byref(st))
@@ -1015,7 +1108,8 @@ class rl_grpc_limiter(_Sized):
 
 class rl_grpc_opts(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("io_threads", C.c_uint32), ("host", C.c_char_p), ("port", C.c_int32),
-                ("isolate", C.c_int32), ("clock_start_ns", C.c_int64), ("clock_step_ns", C.c_int64)]
+                ("isolate", C.c_int32), ("clock_start_ns", C.c_int64), ("clock_step_ns", C.c_int64),
+                ("tally", C.c_int32), ("names_cap", C.c_uint32)]
 
 
 class rl_grpc_stats(_Sized):
@@ -1026,12 +1120,15 @@ class rl_grpc_stats(_Sized):
 class GrpcServer:
     """rl_grpc_server (include/rl_grpc.h): the rate limiter service served by
     native event loops over `coalescer`.  limiters: (name, cfg_id, algorithm,
-    limit, window_ns, prefix, fail_open) tuples, already registered.  With
+    limit, window_ns, prefix, fail_open) tuples, already registered.  tally:
+    serve RateLimiterMetrics.Usage (the coalescer was created with
+    tally_key_slots) and remember the names of the last names_cap (0 = 4096)
+    keys a denied response went out for.  With
     clock_step_ns != 0 the server's time.Now() is the test clock
     clock_start_ns + k * clock_step_ns on its k-th read."""
 
     def __init__(self, coalescer, limiters, host="127.0.0.1", port=0, io_threads=4, isolate=False,
-                 clock_start_ns=0, clock_step_ns=0):
+                 clock_start_ns=0, clock_step_ns=0, tally=False, names_cap=0):
         L = grpc_lib()
         self._lims = (rl_grpc_limiter * max(1, len(limiters)))()
         for i, (name, cfg, alg, limit, window, prefix, fail_open) in enumerate(limiters):
@@ -1039,7 +1136,8 @@ class GrpcServer:
                                             limit=limit, window_ns=window,
                                             prefix=prefix if isinstance(prefix, bytes) else prefix.encode())
         self._opts = rl_grpc_opts(io_threads=io_threads, host=host.encode(), port=port, isolate=int(isolate),
-                                  clock_start_ns=clock_start_ns, clock_step_ns=clock_step_ns)
+                                  clock_start_ns=clock_start_ns, clock_step_ns=clock_step_ns, tally=int(tally),
+                                  names_cap=names_cap)
         self.co = coalescer
         h = vp()
         rc = L.rl_grpc_server_start(coalescer.h, C.cast(self._lims, C.c_void_p), len(limiters),

@@ -22,6 +22,7 @@ _SCALARS = {
     "double": _F.TYPE_DOUBLE, "float": _F.TYPE_FLOAT, "int64": _F.TYPE_INT64, "uint64": _F.TYPE_UINT64,
     "int32": _F.TYPE_INT32, "uint32": _F.TYPE_UINT32, "bool": _F.TYPE_BOOL, "string": _F.TYPE_STRING,
     "bytes": _F.TYPE_BYTES, "sint64": _F.TYPE_SINT64, "sint32": _F.TYPE_SINT32,
+    "fixed64": _F.TYPE_FIXED64, "fixed32": _F.TYPE_FIXED32,
 }
 
 
@@ -216,6 +217,17 @@ def reset_batch(stub, pairs, **kw):
     a = api("ratelimiter.proto")
     req = a.ResetBatchRequest(requests=[a.ResetRequest(limiter=l, key=k) for l, k in pairs])
     return list(stub.ResetBatch(req, **kw).errors)
+
+
+def metrics_stub(channel):
+    """the observability service (RateLimiterMetrics: Usage)"""
+    return Stub(channel, api("ratelimiter.proto"), "RateLimiterMetrics")
+
+
+def usage(stub, top: int = 0, clear: bool = False, **kw):
+    """RateLimiterMetrics.Usage (stub: metrics_stub(channel)) -> UsageResponse: per limiter the requests allowed,
+    denied, failed and invalid and the units, the `top` most denied keys, what the key table could not track"""
+    return stub.Usage(api("ratelimiter.proto").UsageRequest(top=top, clear=clear), **kw)
 
 
 def health_stub(channel):

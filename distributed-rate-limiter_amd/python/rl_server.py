@@ -126,7 +126,15 @@ class RateLimiterService:
     backend).  `register(alg, limit, window_ns) -> cfg_id` registers a config
     with the backend; `clock()` -> Unix ns (time.Now())."""
 
-    def __init__(self, limiters, coalescer, register, clock=time.time_ns, isolate=False):
+    def __init__(self, limiters, coalescer, register, clock=time.time_ns, isolate=False, tally=False,
+                 names_cap=4096):
+        # tally: serve RateLimiterMetrics.Usage from the coalescer's usage
+        # tally (created with tally_key_slots), and remember the names of the
+        # last names_cap keys a denied response went out for (newest wins)
+        self.tally = tally
+        self.names_cap = names_cap
+        self.names = {}                      # key id -> name, in insertion order
+        self.names_lock = threading.Lock()
         self.a = rl_grpc.api("ratelimiter.proto")
         self.h = rl_grpc.api("health.proto")
         self.co = coalescer
@@ -186,14 +194,55 @@ class RateLimiterService:
         if n <= 0:
             ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, ERR_INVALID_N)
         t = self.clock()
-        rc, (dec, rem, retry, reset) = self.co.decide(self._key_id(lim, key), t, n, lim.cfg_id,
-                                                      deadline_ns=self._deadline(ctx))
+        kid = self._key_id(lim, key)
+        rc, (dec, rem, retry, reset) = self.co.decide(kid, t, n, lim.cfg_id, deadline_ns=self._deadline(ctx))
+        if rc == rl_amd.RL_OK and dec == rl_amd.DENIED:
+            self._remember(kid, key)
         res, err, code = self._result(lim, t, rc, dec, rem, retry, reset)
         if err:
             ctx.abort(code, err)
         return res
 
+    def _remember(self, kid: int, key: str):
+        """the name of a key a denied response goes out for (Usage reports it)"""
+        if not self.tally or self.names_cap <= 0:
+            return
+        with self.names_lock:
+            self.names.pop(kid, None)
+            self.names[kid] = key
+            while len(self.names) > self.names_cap:
+                del self.names[next(iter(self.names))]
+
     # -- RPCs ----------------------------------------------------------------
+    def Usage(self, req, ctx):
+        """one rl_coalescer_tally, in sequence order (blocks this handler
+        thread, not the server)"""
+        if not self.tally:
+            ctx.abort(grpc.StatusCode.FAILED_PRECONDITION, "usage tally is off")
+        top = min(req.top, 1 << 16)
+        # rows for this server's limiters: up to their highest config id
+        rows = 1 + max((lim.cfg_id for lim in self.by_name.values()), default=0)
+        rc, t = self.co.tally(top=top, clear=req.clear, max_configs=rows)
+        if rc == rl_amd.RL_EINVAL:
+            ctx.abort(grpc.StatusCode.FAILED_PRECONDITION, "usage tally is off")
+        if rc != rl_amd.RL_OK:
+            ctx.abort(grpc.StatusCode.UNAVAILABLE, f"failed to read usage: engine status {rc}")
+        by_cfg = {lim.cfg_id: lim for lim in reversed(list(self.by_name.values()))}
+        out = self.a.UsageResponse(untracked_requests=t.info.untracked_requests, keys_tracked=t.keys_tracked)
+        for lim in self.by_name.values():
+            c = t.cfg[lim.cfg_id] if lim.cfg_id < t.cfg.size else None
+            out.limiters.add(limiter=lim.name, **({} if c is None else dict(
+                allowed=int(c["count"][rl_amd.ALLOWED]), denied=int(c["count"][rl_amd.DENIED]),
+                errors=int(c["count"][rl_amd.ERROR]), invalid=int(c["count"][rl_amd.INVALID]),
+                units_allowed=int(c["units"][1]), units_denied=int(c["units"][0]))))
+        with self.names_lock:
+            names = {int(r["key_id"]): self.names.get(int(r["key_id"]), "") for r in t.keys}
+        for r in t.keys:
+            lim = by_cfg.get(int(r["cfg_id"]))
+            out.keys.add(limiter=lim.name if lim else "", key_hash=int(r["key_id"]), key=names[int(r["key_id"])],
+                         denied=int(r["denied"]), units_denied=int(r["units_denied"]))
+        return out
+
     def Allow(self, req, ctx):
         return self._allow_n(req.limiter, req.key, 1, ctx)
 
@@ -280,6 +329,8 @@ class RateLimiterService:
             rc, (dec, rem, retry, reset) = self.co.wait(tk, len(idx))
             for j, i in enumerate(idx):
                 lim = self.by_name[rs[i].limiter]
+                if rc == rl_amd.RL_OK and dec[j] == rl_amd.DENIED:
+                    self._remember(int(kid[j]), rs[i].key)
                 res, err, _ = self._result(lim, t, rc, int(dec[j]), int(rem[j]), int(retry[j]), int(reset[j]))
                 out[i] = res if res is not None else self.a.AllowResponse(error=err)
         return self.a.AllowBatchResponse(results=out)
@@ -295,7 +346,7 @@ def build_server(service: RateLimiterService, address: str, workers: int = 64) -
     server = grpc.server(futures.ThreadPoolExecutor(max_workers=workers),
                          options=[("grpc.so_reuseport", 0)])
     for a, sname, impl in ((service.a, "RateLimiter", service), (service.a, "RateLimiterStatus", service),
-                           (service.a, "RateLimiterAdmin", service),
+                           (service.a, "RateLimiterAdmin", service), (service.a, "RateLimiterMetrics", service),
                            (service.h, "Health", service)):
         handlers = {}
         for mname, inp, out in a.services[sname]:
@@ -316,10 +367,11 @@ class GpuBackend:
         self.register = self.eng.register
         self.co = None
 
-    def start(self, max_batch=1 << 16, gc_interval_ns=NS, gc_margin_ms=1000):
-        """the coalescer, with the tables collected from the serving path"""
+    def start(self, max_batch=1 << 16, gc_interval_ns=NS, gc_margin_ms=1000, tally_key_slots=0):
+        """the coalescer, with the tables collected from the serving path
+        (tally_key_slots != 0: with the usage tally, RateLimiterMetrics.Usage)"""
         self.co = rl_amd.Coalescer(self.eng, max_batch=max_batch, max_in_flight=3, gc_interval_ns=gc_interval_ns,
-                                   gc_margin_ms=gc_margin_ms)
+                                   gc_margin_ms=gc_margin_ms, tally_key_slots=tally_key_slots)
         return self.co
 
     def close(self):
@@ -345,14 +397,15 @@ def serve(service, address, workers=64, grace_s=5.0, ready=None, stop_event=None
     return port
 
 
-def serve_native(co, limiters, address, io_threads=4, isolate=False, grace_s=5.0, ready=None, stop_event=None):
+def serve_native(co, limiters, address, io_threads=4, isolate=False, grace_s=5.0, ready=None, stop_event=None,
+                 tally=False):
     """the native front end (include/rl_grpc.h) until SIGTERM / SIGINT (or
     stop_event): then health NOT_SERVING, stop accepting, answer the RPCs in
     flight within grace_s"""
     host, port = address.rsplit(":", 1)
     srv = rl_amd.GrpcServer(co, [(l.name, l.cfg_id, l.alg, l.limit, l.window_ns, l.prefix, l.fail_open)
                                  for l in limiters], host=host, port=int(port), io_threads=io_threads,
-                            isolate=isolate)
+                            isolate=isolate, tally=tally)
     try:
         if ready:
             ready(srv.port)
@@ -392,6 +445,8 @@ def main(argv=None):
     ap.add_argument("--isolate-limiters", action="store_true",
                     help="one key namespace per limiter (the reference shares state between limiters with "
                          "the same prefix, as Redis keys are the formatted strings)")
+    ap.add_argument("--tally-key-slots", type=int, default=0,
+                    help="usage tally (RateLimiterMetrics.Usage): records of the throttled-key table, 0 = off")
     args = ap.parse_args(argv)
     specs = args.limiter or ["default:token_bucket:20:12s"]
     limiters = [Limiter.parse(s) for s in specs]
@@ -403,12 +458,14 @@ def main(argv=None):
             for lim in limiters:
                 lim.cfg_id = be.register(lim.alg, lim.limit, lim.window_ns)
             co = be.start(args.max_batch, int(args.gc_interval_ms * 1e6),
-                          args.gc_margin_ms)
+                          args.gc_margin_ms, args.tally_key_slots)
             serve_native(co, limiters, args.address, args.io_threads, args.isolate_limiters,
-                         ready=lambda p: print(f"READY {p}", flush=True))
+                         ready=lambda p: print(f"READY {p}", flush=True), tally=args.tally_key_slots != 0)
         else:
-            svc = RateLimiterService(limiters, None, be.register, isolate=args.isolate_limiters)
-            svc.co = be.start(args.max_batch, int(args.gc_interval_ms * 1e6), args.gc_margin_ms)
+            svc = RateLimiterService(limiters, None, be.register, isolate=args.isolate_limiters,
+                                     tally=args.tally_key_slots != 0)
+            svc.co = be.start(args.max_batch, int(args.gc_interval_ms * 1e6), args.gc_margin_ms,
+                              args.tally_key_slots)
             serve(svc, args.address, args.workers, ready=lambda p: print(f"READY {p}", flush=True))
     finally:
         be.close()

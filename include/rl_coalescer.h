@@ -89,6 +89,11 @@ typedef struct rl_coalescer_opts {
     int64_t  gc_margin_ms;         /* 0 = 1000 */
     uint64_t gc_max_tb_capacity;   /* growth limits (0 = no limit but the engine's) */
     uint64_t gc_max_win_capacity;
+    /* Usage tally (rl_tally_*, rl_engine.h): 0 = off; otherwise the records of
+     * the throttled-key table (rounded up to a power of 2, 16 .. 1<<24), and
+     * every launched batch of requests is counted behind its decisions (a
+     * caller compiled before this field passes the shorter struct_size: off) */
+    uint32_t tally_key_slots;
 } rl_coalescer_opts;
 
 typedef struct rl_coalescer_stats {
@@ -231,6 +236,22 @@ int rl_coalescer_snapshot(rl_coalescer* c, int64_t now_ms, uint32_t world, uint3
 int rl_coalescer_restore(rl_coalescer* c, const void* buf, size_t len, int64_t now_ms,
                          uint64_t tb_capacity, uint64_t win_capacity, rl_table_info* out);
 int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out);
+/* The usage tally (rl_tally_read's arguments, rl_engine.h) in sequence order
+ * like rl_coalescer_table_info: it has counted every request submitted before
+ * the call and none submitted after; nothing is drained.  With
+ * tally_key_slots the submitter enqueues rl_tally_batch_device behind every
+ * batch of requests, on that batch's stream (its buffers are not reused before
+ * the tally has run).  Peeks and resets are not counted, nor are requests
+ * dropped unapplied (deadline, cancel).  Blocks until done.  RL_EINVAL when
+ * tally_key_slots was 0.
+ * Over a host backend the coalescer keeps the same tally itself, on the host:
+ * the same table rule and probe bound.  A host backend registers no configs,
+ * so there a config id is known from the first request of it that the backend
+ * decides (any decision but RL_INVALID); an RL_INVALID request of a config id
+ * not known yet adds to unknown_cfg. */
+int rl_coalescer_tally(rl_coalescer* c, rl_tally_cfg* cfg_out, size_t cfg_cap, uint32_t* ncfg,
+                       rl_tally_key* key_out, size_t key_cap, uint64_t* keys_tracked,
+                       rl_tally_info* info, int clear);
 
 #ifdef __cplusplus
 }

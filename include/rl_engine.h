@@ -275,6 +275,67 @@ int rl_last_error(rl_engine* e, char* buf, size_t len);
 int rl_selftest_q14_host(const double* in, double* out, size_t n);
 int rl_selftest_q14_device(rl_engine* e, const double* in, double* out, size_t n);
 
+/* Usage tally: what the decisions were, counted on the device -- per config
+ * the requests by decision code and the units granted and denied, and the keys
+ * that are being throttled.  Off until rl_tally_enable; it reads result arrays
+ * only and never touches the state tables, rl_stats or the sticky status of
+ * rl_engine_sync.  Every rl_tally_* call before rl_tally_enable is RL_EINVAL.
+ *
+ * Per request (key_id, cfg_id, n, decision): an unregistered cfg_id adds one to
+ * unknown_cfg and nothing else; otherwise a decision byte above 3 adds one to
+ * bad_codes and nothing else; otherwise count[decision] of the config grows by
+ * one and, for RL_DENIED / RL_ALLOWED with n > 0, units[decision] by n (modulo
+ * 2^64).  Every key with a denied request is recorded in a table of key_slots
+ * records (open addressing from mix64(key_id) & (key_slots - 1), at most
+ * min(key_slots, 64) probes): its denied requests and their units.  The table
+ * only fills until the next clear, so a key is tracked completely or not at
+ * all; the denied requests of keys without a slot (and of RL_KEY_RESERVED) are
+ * summed in untracked_requests / untracked_units. */
+typedef struct rl_tally_opts {
+    uint32_t struct_size;   /* sizeof(rl_tally_opts) */
+    uint32_t key_slots;     /* rounded up to a power of 2, 16 .. 1<<24; 0 = 65536 */
+} rl_tally_opts;
+typedef struct rl_tally_cfg {
+    uint64_t count[4];      /* by decision code: RL_DENIED, RL_ALLOWED, RL_ERROR, RL_INVALID */
+    uint64_t units[2];      /* sum of n: [0] denied, [1] allowed */
+} rl_tally_cfg;
+typedef struct rl_tally_key {
+    uint64_t key_id, denied, units_denied;
+    uint32_t cfg_id, pad_;  /* cfg_id: the config of one of the key's denied requests */
+} rl_tally_key;
+typedef struct rl_tally_info {
+    uint32_t struct_size, pad_;   /* sizeof(rl_tally_info) */
+    uint64_t key_slots, keys_tracked, untracked_requests, untracked_units, unknown_cfg, bad_codes;
+    uint64_t batches, requests;   /* rl_tally_batch(_device) calls with m > 0 / their requests */
+} rl_tally_info;
+/* allocates the accumulators; a second call is RL_EINVAL.  A config registered
+ * later gets a zero row. */
+int rl_tally_enable(rl_engine* e, const rl_tally_opts* opts);
+/* Count one finished batch in the decide layout (device pointers), on `stream`
+ * (a hipStream_t; NULL = the engine's stream): queued after
+ * rl_decide_batch_device on the same stream it sees that batch's results.  The
+ * arrays must stay unmodified until the stream has passed the call.  m may
+ * exceed max_batch; m == 0 is RL_OK without a launch; null arrays with m > 0
+ * are RL_EINVAL. */
+int rl_tally_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const uint32_t* cfg_id,
+                          const int64_t* n, const uint8_t* decision, void* stream);
+/* the same with host arrays; synchronous */
+int rl_tally_batch(rl_engine* e, size_t m, const uint64_t* key_id, const uint32_t* cfg_id,
+                   const int64_t* n, const uint8_t* decision);
+/* Synchronous: waits for every tally call made before it, on any stream.
+ * Writes the rows of configs 0 .. min(cfg_cap, *ncfg) - 1 (*ncfg: the configs
+ * registered) and the key_cap tracked keys with the most denied requests,
+ * ordered by denied descending, then key_id ascending (fewer when fewer are
+ * tracked; *keys_tracked: how many are).  Every output is nullable.  With
+ * clear != 0 everything is zeroed after the copy, before any later tally
+ * call. */
+int rl_tally_read(rl_engine* e, rl_tally_cfg* cfg_out, size_t cfg_cap, uint32_t* ncfg,
+                  rl_tally_key* key_out, size_t key_cap, uint64_t* keys_tracked,
+                  rl_tally_info* info, int clear);
+/* requests one k_tally launch covers with one request per thread (grid cap x
+ * block size); a larger batch strides */
+int rl_tally_grid_cap(void);
+
 #ifdef __cplusplus
 }
 #endif

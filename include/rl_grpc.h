@@ -74,6 +74,15 @@ typedef struct rl_grpc_opts {
      * time (deterministic decisions for the parity tests) */
     int64_t clock_start_ns;
     int64_t clock_step_ns;
+    /* RateLimiterMetrics.Usage: != 0 serves it from the coalescer's usage tally
+     * (rl_coalescer_opts.tally_key_slots; one rl_coalescer_tally per RPC,
+     * completed through the ticket's notification like every RPC) and keeps the
+     * names of the last names_cap keys a denied response went out for (0 =
+     * 4096; newest wins), which Usage reports beside the key ids.  0, or a
+     * caller compiled before these fields (the shorter struct_size):
+     * FAILED_PRECONDITION. */
+    int32_t tally;
+    uint32_t names_cap;
 } rl_grpc_opts;
 
 typedef struct rl_grpc_stats {
@@ -86,7 +95,10 @@ typedef struct rl_grpc_stats {
     uint64_t cancelled;      /* RPCs the client reset before their response */
 } rl_grpc_stats;
 
-/* Start serving on the coalescer (which must outlive the server).  The
+/* Start serving on the coalescer, which must outlive the server: destroy the
+ * server first (rl_grpc_server_destroy waits, up to 10 s, for a Usage read the
+ * coalescer still has queued or running, since that read writes into memory
+ * the server owns).  The
  * limiters are copied.  *out gets the server; it listens when this returns. */
 int rl_grpc_server_start(rl_coalescer* c, const rl_grpc_limiter* limiters, size_t n_limiters,
                          const rl_grpc_opts* opts, rl_grpc_server** out);
