@@ -12,6 +12,12 @@
 // Reference boundary replaced: go-redis Eval + Redis Lua + the Go arithmetic
 // around it (tokenbucket.go:90-193, slidingwindow.go:68-185,
 // fixedwindow.go:65-163); see include/rl_engine.h.
+//
+// This unit is the decision path and the engine's life cycle only.  Peek and
+// Reset are rl_ops.hip, table maintenance and snapshots rl_tables.hip, the
+// usage tally rl_tally.hip, each a code object of its own, so that of the
+// decision kernels changes with none of them; rl_engine_impl.h is what they
+// share.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -26,80 +32,17 @@
 #include "../../include/rl_engine.h"
 #include "../../include/rl_keyhash.h"
 #include "../../include/rl_route.h"
-#include "../../include/rl_snapshot.h"
-#include "rl_peek.h"
-#include "rl_reset.h"
+#include "rl_engine_impl.h"
 #include "rl_replay.h"
 #include "rl_semantics.h"
-#include "rl_snapshot.h"
 #include "rl_sort.h"
 #include "rl_table.h"
-#include "rl_tally.h"
 
 using namespace rl;
 
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
-
-__global__ void k_init_tb(TbEntry* t, uint64_t n) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        t[i].key = EMPTY_KEY;
-        t[i].tok = 0.0;
-        t[i].last = 0.0;
-        t[i].when = ABSENT;
-    }
-}
-
-__global__ void k_init_win(WinEntry* t, uint64_t n) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        t[i].key = EMPTY_KEY;
-        t[i].nspill = 0;
-        for (int k = 0; k < 2; k++) { t[i].s[k].ws = 0; t[i].s[k].cnt = 0; t[i].s[k].when = ABSENT; }
-    }
-}
-
-// Table GC of the spill table, after the window table's k_rehash: every live
-// spill entry moves to the fresh spill table (strict CAS: two entries of one
-// user key may be moved at once) and is counted in its user key's new window
-// entry, which is inserted here (empty) if k_rehash dropped the old one as
-// expired.  counters as k_rehash.
-__global__ void k_spill_rehash(const SpillEntry* __restrict__ old, uint64_t n_old, SpillEntry* nu, uint64_t mask_new,
-                               WinEntry* win, uint64_t win_mask, int64_t now_ms, int32_t profile,
-                               unsigned long long* counters) {
-    unsigned long long live = 0, lost = 0;
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_old;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const SpillEntry x = old[i];
-        if (!entry_live(x, now_ms, profile)) continue;
-        live++;
-        const uint32_t w = probe_insert(win, win_mask, x.key);
-        uint64_t h = spill_home(x.key, mask_new);
-        bool placed = false;
-        for (uint64_t p = 0; w != NO_SLOT && p <= mask_new && p < MAX_PROBES; p++) {
-            if (atomicCAS((unsigned long long*)&nu[h].key, (unsigned long long)EMPTY_KEY,
-                          (unsigned long long)x.key) == EMPTY_KEY) {
-                nu[h].ws = x.ws;
-                nu[h].cnt = x.cnt;
-                nu[h].when = x.when;
-                atomicAdd((unsigned long long*)&win[w].nspill, 1ull);
-                placed = true;
-                break;
-            }
-            h = (h + 1) & mask_new;
-        }
-        if (!placed) lost++;
-    }
-    if (live) atomicAdd(&counters[0], live);
-    if (lost) atomicAdd(&counters[1], lost);
-}
-
-__global__ void k_init_spill(SpillEntry* t, uint64_t n) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        t[i] = SpillEntry{EMPTY_KEY, 0, 0, ABSENT};
-}
 
 constexpr int PROBE_BLOCK = 256;
 
@@ -376,49 +319,6 @@ __global__ __launch_bounds__(SMALL_BLOCK) void k_small(
     if (ef) atomicOr(eflags, ef);
 }
 
-// Reset: DEL of the key(s) AllowN would touch at ts (tokenbucket.go:136-144,
-// slidingwindow.go:125-139, fixedwindow.go:118-128)
-__global__ void k_reset(uint64_t key, int64_t ts, const CfgDev* cfgs, uint32_t cfg, TbEntry* tb,
-                        uint64_t tb_mask, WinEntry* win, uint64_t win_mask, Spill spill) {
-    const CfgDev& c = cfgs[cfg];
-    if (c.alg == ALG_TOKEN_BUCKET) {
-        uint32_t s = probe_find(tb, tb_mask, key);
-        if (s != NO_SLOT) tb[s].when = ABSENT;
-        return;
-    }
-    uint32_t s = probe_find(win, win_mask, key);
-    if (s == NO_SLOT) return;
-    const int64_t ws = window_start(ts, c);
-    wk_delete(&win[s], spill, ws);
-    if (c.alg == ALG_SLIDING_WINDOW) wk_delete(&win[s], spill, ws - c.ttl_c);
-}
-
-// Redis KEYS (rl_table_keys): every live key of the three tables
-__device__ inline void key_emit(rl_key_rec* out, uint64_t cap, unsigned long long* cnt, uint64_t k, int64_t ws,
-                                uint32_t kind) {
-    const unsigned long long i = atomicAdd(cnt, 1ull);
-    if (i < cap) out[i] = rl_key_rec{k, ws, kind, 0};
-}
-__global__ void k_table_keys(const TbEntry* tb, uint64_t ntb, const WinEntry* win, uint64_t nwin,
-                             const SpillEntry* sp, uint64_t nsp, int64_t now_ms, int32_t profile, rl_key_rec* out,
-                             uint64_t cap, unsigned long long* cnt) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < ntb + nwin + nsp; i += stride) {
-        if (i < ntb) {
-            if (entry_live(tb[i], now_ms, profile)) key_emit(out, cap, cnt, tb[i].key, 0, RL_KIND_HASH);
-        } else if (i < ntb + nwin) {
-            const WinEntry& x = win[i - ntb];
-            if (x.key == EMPTY_KEY) continue;
-            for (int k = 0; k < 2; k++)
-                if (x.s[k].when != ABSENT && key_alive(x.s[k].when, now_ms, profile))
-                    key_emit(out, cap, cnt, x.key, x.s[k].ws, RL_KIND_WINDOW);
-        } else {
-            const SpillEntry& x = sp[i - ntb - nwin];
-            if (entry_live(x, now_ms, profile)) key_emit(out, cap, cnt, x.key, x.ws, RL_KIND_WINDOW);
-        }
-    }
-}
-
 // results of a routed batch: one 32-byte result record per request at its
 // receive index (the send layout of the result all-to-all)
 __global__ __launch_bounds__(256) void k_unpermute_routed(const uint32_t* __restrict__ sk,
@@ -490,9 +390,7 @@ __global__ void k_q14(const double* in, double* out, uint32_t n) {
 
 namespace {
 
-constexpr int NSTAGES = 5;
 constexpr uint32_t STAMP_RING = 256;
-constexpr int NSETS = 3;          // batch buffer sets: grouping b+1 | replay b | finish b-1
 constexpr uint32_t LIGHT_MIN_BATCH = 1u << 19;   // batches this large may take k_replay_light
 constexpr int GROUP_LDS = 4096;   // LDS floor of the grouping / finish kernels (see rl_engine::chain_pad)
 // A set's zeroed words.  The head (list counts, queues, diagnostics) is read
@@ -527,196 +425,54 @@ static uint32_t sort_shifts(int bits, int passes) {
     return sh;
 }
 
-uint64_t pow2_at_least(uint64_t v) {
-    uint64_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
 int bitlen(uint64_t v) {
     int b = 0;
     while (v) { b++; v >>= 1; }
     return b;
 }
 
-}  // namespace
-
-// Per-batch device buffers.  A batch runs in three parts on three engine
-// streams: grouping (probe, sort, segments, permute) on `front`, the replay
-// (k_tb_chain) on `chain`, the finish (run expansion, unpermute) on `tail`.
-// The replays are ordered on `chain` (each one reads the table state the
-// previous one wrote); nothing else orders batches, so batch b+1's grouping
-// and batch b-1's finish overlap batch b's replay.  NSETS buffer sets: set
-// b mod NSETS is reused by batch b+NSETS only after batch b's finish.  The
-// caller's stream waits for the finish of every batch it enqueued.
-struct BatchSet {
-    uint32_t *sk0 = nullptr, *sk1 = nullptr, *sv0 = nullptr, *sv1 = nullptr;
-    SegRec* list[4] = {nullptr, nullptr, nullptr, nullptr};   // heavy TB, light, heavy window, huge TB
-    // requests and results in sorted order (k_permute / k_unpermute)
-    int64_t *p_ts = nullptr, *p_n = nullptr, *p_sms = nullptr;
-    uint32_t* p_cfg = nullptr;
-    void* rec = nullptr;          // requests packed in arrival order (k_probe -> k_permute): ReqRec<XS>
-    void* recb = nullptr;         // ReqRec in the MSD pass's bucket order (k_sort_pass -> k_permute)
-    // an explicit server clock's record fields that do not fit (rec_pack), by arrival index
-    int64_t* side_n = nullptr;
-    uint32_t* side_cfg = nullptr;
-    int64_t* side_sms = nullptr;
-    uint8_t* p_fresh = nullptr;   // sorted order: the request inserted its key (k_permute -> replay phase 3)
-    uint8_t* o_dec = nullptr;
-    double* o_tok = nullptr;      // tokens (token bucket) / Remaining bits (window): finish_result
-    // token-bucket precomputation (k_permute)
-    double *q_add = nullptr, *q_th = nullptr;
-    TbRuns runs{};                // the chain's committed runs (by start position)
-    uint32_t* zero = nullptr;     // ctrl words + look-back status + huge claims (zeroed per batch)
-    bool dirty = false;           // a batch began on the set and did not reach its finish's zeroing
-    uint32_t* ctrl = nullptr;
-    uint32_t* status = nullptr;
-    uint32_t* claim = nullptr;
-    hipEvent_t front_done = nullptr, chain_done = nullptr, back_done = nullptr;
-    uint64_t* kid = nullptr;      // key ids hashed from raw keys (rl_decide_batch_keys_device; lazy)
-    UpRec* upb = nullptr;         // results bucketed by arrival index (k_unpermute_bucket)
-    bool used = false;
-};
-
-struct rl_engine {
-    int device = 0;
-    int32_t profile = PROFILE_REDIS7;
-    uint32_t flags = 0;
-    // the engine's stream (host API, device API without a stream, setup) is
-    // `tail`: with the caller's stream the engine then uses four streams, one
-    // hardware queue each at HIP's default of four queues per process (streams
-    // sharing a queue would serialize the replay and the finish)
-    hipStream_t stream = nullptr;
-    hipStream_t front = nullptr;      // grouping
-    hipStream_t chain = nullptr;      // replays, in batch order
-    hipStream_t tail = nullptr;       // finishes
-    hipEvent_t ev_in = nullptr;       // inputs ready (non-pipelined device API, host API)
-    std::string err;
-
-    std::vector<CfgDev> h_cfg;
-    CfgDev* d_cfg = nullptr;
-    uint32_t cfg_cap = 0;
-
-    TbEntry* d_tb = nullptr;
-    uint64_t tb_cap = 0;
-    WinEntry* d_win = nullptr;
-    uint64_t win_cap = 0;
-    SpillEntry* d_spill = nullptr;    // window keys outside their user key's entry (rl_window.h)
-    uint64_t spill_cap = 0;
-    bool spill_follows = true;        // spill capacity = 2 x window capacity (also after a resize)
-    Spill spill() const { return Spill{d_spill, spill_cap - 1}; }
-    uint32_t win_base = 0, invalid_key = 0;
-    int sort_bits = 0, sort_passes = 0;
-    uint32_t sort_shifts = 0;   // digit shift of each histogram / pass (8 bits each; sort_shifts())
-
-    uint32_t max_batch = 0;
-    uint32_t max_tiles = 0;
-    BatchSet set[NSETS];
-    // k_small: batches up to small_max run as one workgroup on `chain`; its
-    // sorted-order scratch (reused by consecutive small batches, which the
-    // chain stream orders)
-    uint32_t small_max = 0;
-    // batches up to up_max finish through arrival-index buckets, larger ones
-    // through k_unpermute / k_unpermute_routed (RL_UP_MAX lowers it: the
-    // buckets and their counters are sized for UP_MAX)
-    uint32_t up_max = UP_MAX;
-    int64_t *s_ts = nullptr, *s_n = nullptr, *s_sms = nullptr;
-    uint32_t* s_cfg = nullptr;
-    uint8_t* s_dec = nullptr;
-    double *s_tok = nullptr, *s_add = nullptr, *s_th = nullptr;
-    hipEvent_t ev_small = nullptr;
-    hipEvent_t ev_reset = nullptr;    // rl_reset_device: the DEL on `chain` -> the caller's stream
-    hipEvent_t ev_peek = nullptr;     // rl_peek_batch_device: k_peek on `chain` -> the caller's stream
-    int next_set = 0, last_set = 0;   // set of the next / the last enqueued batch
-    size_t zero_bytes = 0;
-    int coop_grid = 128;        // k_tb_chain blocks launched (one per CU fits its LDS) ...
-    int coop_base = 112;        // ... of which those past 112 of 256 CUs exit at once unless the batch
-                                // has at least m / coop_light_div light segments: the other CUs run
-                                // the neighbouring batches' grouping and finish (profiles/r3al_ab_replay_grid.txt;
-                                // 96 -> 112 with the iterative-ILP build: configs[1] +1.1-1.5 %,
-                                // profiles/r6zm_ab_coop_base.txt)
-    uint32_t coop_light_div = 4;
-    int probe_grid = 1024;      // k_probe blocks at most
-    int perm_grid = 1024;       // k_permute / k_unpermute blocks at most
-    uint32_t heavy_min = 32;    // segments this long replay cooperatively
-    uint32_t huge_min = 4096;   // token-bucket segments this long are dequeued first
-    // dynamic LDS that makes a k_tb_chain block fill its CU's LDS: with two
-    // batches in flight, the other batches' grouping and finish kernels (each launched with
-    // GROUP_LDS bytes at least) then never share a CU with a chain
-    size_t chain_pad[2] = {0, 0};
-    size_t light_pad[2] = {0, 0};    // k_replay_light: the same one-block-per-CU LDS floor
-    uint32_t* h_huge = nullptr;      // mapped host word: huge segments of the last replay seen (k_tb_chain /
-    uint32_t* d_huge = nullptr;      //   k_replay_light write it); 0 -> the next batches launch k_replay_light
-    bool light_ok = true;            // RL_NO_LIGHT_REPLAY=1: always the chain kernel
-    bool force_light = false;        // warm-up: load k_replay_light
-    uint32_t* d_eflags = nullptr;
-    uint32_t* d_zero = nullptr;       // a device word holding 0 (warm-up of the routed kernels)
-    unsigned long long* d_count = nullptr;   // table counts / GC counters (rl_table_info_get, rl_table_gc)
-    unsigned long long* h_count = nullptr;   // pinned host copy
-    // the grouping sort's last plan (1: every MSD bucket fit LDS), written by
-    // the MSD pass into mapped host memory; read when a batch is enqueued
-    uint32_t* h_plan = nullptr;
-    uint32_t* d_plan = nullptr;   // its device address
-    uint32_t* stamp_ring = nullptr;   // RL_STAMP_KERNELS diagnostics
-
-    // host-API staging (device side)
-    uint64_t* d_key = nullptr;
-    uint64_t* small_kid = nullptr;   // key ids hashed for k_small (rl_decide_batch_keys_device; lazy)
-    int64_t *d_ts = nullptr, *d_n = nullptr, *d_sms = nullptr;
-    uint32_t* d_cfgid = nullptr;
-    uint8_t* d_dec = nullptr;
-    int64_t *d_rem = nullptr, *d_retry = nullptr, *d_reset = nullptr;
-    double* d_tok = nullptr;
-
-    // timing: front start, after probe, after sort, after segments+permute
-    // (front); replay start, end (chain); finish start, end (tail)
-    bool timing = false;
-    bool timing_all = false;    // level 2: every stage; level 1: the replay only (2 events per batch)
-    uint32_t timing_stride = 1; // the replay events on every timing_stride-th batch only (level -k)
-    uint64_t timing_seq = 0;
-    bool stamps = false;        // RL_STAMP_KERNELS: timestamps around each replay (debug words 18, 19)
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<std::array<hipEvent_t, 8>> ev_pending;
-    double stage_ms[NSTAGES] = {0, 0, 0, 0, 0};
-    uint64_t timed_batches = 0;
-
-    rl_stats stats{};
-
-    // usage tally (rl_tally.h): off until rl_tally_enable
-    bool tally_on = false;
-    TallyKey* d_tally_keys = nullptr;
-    uint64_t tally_slots = 0;
-    tally_u64* d_tally_cfg = nullptr;     // TALLY_CFG_WORDS per config, tally_cfg_cap rows
-    uint32_t tally_cfg_cap = 0;
-    tally_u64* d_tally_glob = nullptr;    // TG_WORDS
-    uint64_t tally_batches = 0, tally_requests = 0;
-    // the end of the last tally on each stream one was enqueued on: what
-    // drain() and rl_tally_read wait for (k_tally runs on the caller's stream)
-    std::vector<std::pair<hipStream_t, hipEvent_t>> tally_ev;
-};
-
-static int fail(rl_engine* e, int code, const std::string& msg) {
-    if (e) e->err = msg;
-    return code;
+template <class T>
+hipError_t to_device(T* dst, const T* src, size_t off, uint32_t c, hipStream_t s) {
+    return src ? hipMemcpyAsync(dst, src + off, sizeof(T) * c, hipMemcpyHostToDevice, s) : hipSuccess;
+}
+template <class T>
+hipError_t to_host(T* dst, size_t off, const T* src, uint32_t c, hipStream_t s) {
+    return dst ? hipMemcpyAsync(dst + off, src, sizeof(T) * c, hipMemcpyDeviceToHost, s) : hipSuccess;
 }
 
-#define HIPCHK(e, call)                                                                  \
-    do {                                                                                 \
-        hipError_t _st = (call);                                                         \
-        if (_st != hipSuccess)                                                           \
-            return fail((e), RL_EDEVICE, std::string(#call) + ": " + hipGetErrorString(_st)); \
-    } while (0)
+}  // namespace
 
-// versioned output structs (include/rl_engine.h): the caller's struct_size
-// bounds what is written, and struct_size comes back as the bytes actually
-// filled in (min(caller's, library's)), so a caller built against a newer
-// header sees which trailing fields this library knows; a size smaller than
-// the header field is rejected
-template <class T>
-static int copy_out(T* dst, T src) {
-    if (dst->struct_size < 8) return RL_EINVAL;
-    const uint32_t n = (uint32_t)std::min<size_t>(dst->struct_size, sizeof(T));
-    src.struct_size = n;
-    memcpy(dst, &src, n);
+void rl::set_geometry(rl_engine* e, uint64_t tb_cap, uint64_t win_cap, uint64_t spill_cap) {
+    e->tb_cap = tb_cap;
+    e->win_cap = win_cap;
+    e->spill_cap = spill_cap;
+    // slot ids (the sort keys) follow the capacities
+    e->win_base = (uint32_t)tb_cap;
+    e->invalid_key = (uint32_t)(tb_cap + win_cap);
+    e->sort_bits = bitlen(e->invalid_key);
+    e->sort_passes = (e->sort_bits + 7) / 8;
+    e->sort_shifts = sort_shifts(e->sort_bits, e->sort_passes);
+    e->stats.sort_bits = e->sort_bits;
+    e->stats.sort_passes = e->sort_passes;
+}
+
+int rl::stage_in(rl_engine* e, size_t off, uint32_t c, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                 const uint32_t* cfg, const int64_t* sms, hipStream_t s) {
+    HIPCHK(e, to_device(e->d_key, key, off, c, s));
+    HIPCHK(e, to_device(e->d_ts, ts, off, c, s));
+    HIPCHK(e, to_device(e->d_n, n, off, c, s));
+    HIPCHK(e, to_device(e->d_cfgid, cfg, off, c, s));
+    HIPCHK(e, to_device(e->d_sms, sms, off, c, s));
+    return RL_OK;
+}
+
+int rl::stage_out(rl_engine* e, size_t off, uint32_t c, uint8_t* dec, int64_t* rem, int64_t* retry, int64_t* reset,
+                  double* tok, hipStream_t s) {
+    HIPCHK(e, to_host(dec, off, e->d_dec, c, s));
+    HIPCHK(e, to_host(rem, off, e->d_rem, c, s));
+    HIPCHK(e, to_host(retry, off, e->d_retry, c, s));
+    HIPCHK(e, to_host(reset, off, e->d_reset, c, s));
+    HIPCHK(e, to_host(tok, off, e->d_tok, c, s));
     return RL_OK;
 }
 
@@ -821,9 +577,7 @@ static void free_all(rl_engine* e) {
     if (e->tail) (void)hipStreamDestroy(e->tail);
 }
 
-// every queued kernel of the engine has finished (the engine's streams and,
-// through the back_done events, any caller stream a batch was enqueued on)
-static int drain(rl_engine* e) {
+int rl::drain(rl_engine* e) {
     HIPCHK(e, hipStreamSynchronize(e->front));
     HIPCHK(e, hipStreamSynchronize(e->chain));
     HIPCHK(e, hipStreamSynchronize(e->tail));
@@ -849,17 +603,13 @@ extern "C" int rl_engine_create(const rl_opts* o, rl_engine** out) {
     e->device = o->device;
     e->profile = o->profile;
     e->flags = o->flags;
-    e->tb_cap = pow2_at_least(std::max<uint64_t>(o->tb_capacity, 1024));
-    e->win_cap = pow2_at_least(std::max<uint64_t>(o->win_capacity, 1024));
-    if (e->tb_cap + e->win_cap >= (1ull << 31)) { delete e; return RL_EINVAL; }
+    const uint64_t tb_cap = pow2_at_least(std::max<uint64_t>(o->tb_capacity, 1024));
+    const uint64_t win_cap = pow2_at_least(std::max<uint64_t>(o->win_capacity, 1024));
+    const uint64_t spill_cap =
+        pow2_at_least(std::max<uint64_t>(o->spill_capacity ? o->spill_capacity : 2 * win_cap, 1024));
+    if (!caps_fit(tb_cap, win_cap) || spill_cap > (1ull << 34)) { delete e; return RL_EINVAL; }
     e->spill_follows = o->spill_capacity == 0;
-    e->spill_cap = pow2_at_least(std::max<uint64_t>(o->spill_capacity ? o->spill_capacity : 2 * e->win_cap, 1024));
-    if (e->spill_cap > (1ull << 34)) { delete e; return RL_EINVAL; }
-    e->win_base = (uint32_t)e->tb_cap;
-    e->invalid_key = (uint32_t)(e->tb_cap + e->win_cap);
-    e->sort_bits = bitlen(e->invalid_key);
-    e->sort_passes = (e->sort_bits + 7) / 8;
-    e->sort_shifts = sort_shifts(e->sort_bits, e->sort_passes);
+    set_geometry(e, tb_cap, win_cap, spill_cap);
     e->max_batch = o->max_batch;
     e->max_tiles = (o->max_batch + SORT_TILE - 1) / SORT_TILE;
 
@@ -896,7 +646,8 @@ extern "C" int rl_engine_create(const rl_opts* o, rl_engine** out) {
     if (hipEventCreateWithFlags(&e->ev_peek, hipEventDisableTiming) != hipSuccess) return bail(RL_EDEVICE);
     e->small_max = SMALL_MAX;
     if (const char* v = getenv("RL_SMALL_MAX")) e->small_max = std::min<uint32_t>((uint32_t)atoi(v), SMALL_MAX);
-    if (const char* v = getenv("RL_UP_MAX")) e->up_max = std::min<uint32_t>((uint32_t)std::max(0, atoi(v)), UP_MAX);
+    e->up_max = UP_MAX;
+    if (const char* v = getenv("RL_UP_MAX")) e->up_max =std::min<uint32_t>((uint32_t)std::max(0, atoi(v)), UP_MAX);
     size_t M = e->max_batch;
     e->cfg_cap = 64;
     const size_t status_words = (size_t)4 * e->max_tiles * RADIX;
@@ -915,11 +666,11 @@ extern "C" int rl_engine_create(const rl_opts* o, rl_engine** out) {
     if (ok) {
         *(volatile uint32_t*)e->h_plan = 0u;   // first batches: no prediction (the LSD passes are launched)
         ok &= hipHostGetDevicePointer((void**)&e->d_plan, e->h_plan, 0) == hipSuccess;
-    ok &= hipHostMalloc(&e->h_huge, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+    }
+    ok = ok && hipHostMalloc(&e->h_huge, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
     if (ok) {
         *(volatile uint32_t*)e->h_huge = 1u;   // first batches: the chain kernel
         ok &= hipHostGetDevicePointer((void**)&e->d_huge, e->h_huge, 0) == hipSuccess;
-    }
     }
     ok &= hipMalloc(&e->d_key, 8 * M) == hipSuccess;
     ok &= hipMalloc(&e->d_ts, 8 * M) == hipSuccess;
@@ -938,9 +689,7 @@ extern "C" int rl_engine_create(const rl_opts* o, rl_engine** out) {
     ok &= hipMalloc(&e->s_cfg, 4 * SMALL_MAX) == hipSuccess;
     ok &= hipMalloc(&e->s_dec, SMALL_MAX) == hipSuccess;
     if (!ok) return bail(RL_ENOMEM);
-    k_init_tb<<<2048, 256, 0, e->stream>>>(e->d_tb, e->tb_cap);
-    k_init_win<<<2048, 256, 0, e->stream>>>(e->d_win, e->win_cap);
-    k_init_spill<<<2048, 256, 0, e->stream>>>(e->d_spill, e->spill_cap);
+    tables_init(e->d_tb, e->tb_cap, e->d_win, e->win_cap, e->d_spill, e->spill_cap, e->stream);
     if (hipMemsetAsync(e->d_eflags, 0, 4, e->stream) != hipSuccess) return bail(RL_EDEVICE);
     if (hipStreamSynchronize(e->stream) != hipSuccess) return bail(RL_EDEVICE);
     if (hipDeviceSynchronize() != hipSuccess) return bail(RL_EDEVICE);
@@ -983,8 +732,6 @@ extern "C" int rl_engine_create(const rl_opts* o, rl_engine** out) {
         }
     }
     if (getenv("RL_NO_LIGHT_REPLAY")) e->light_ok = false;
-    e->stats.sort_bits = e->sort_bits;
-    e->stats.sort_passes = e->sort_passes;
     {
         const int r = warm_up(e);
         if (r != RL_OK) return bail(r);
@@ -1373,105 +1120,12 @@ static int run_batch(rl_engine* e, uint32_t m, ReqArgs a, hipStream_t s, bool in
     return RL_OK;
 }
 
-// enqueue one read-only query batch (rl_peek.h) of any size: k_peek on
-// `chain`, between the replays of the batches enqueued before and after it
-// (the replays -- k_tb_chain, k_replay_light, k_small -- and the DEL of a reset
-// are the only writers of entry state, all on `chain`); s waits for it.
-// No per-batch buffer is involved, and nothing is counted in rl_stats.
-static int run_peek(rl_engine* e, size_t m, ReqArgs a, hipStream_t s, bool inputs_ready) {
-    if (m == 0) return RL_OK;
-    hipStream_t c = e->chain;
-    if (!inputs_ready) {
-        HIPCHK(e, hipEventRecord(e->ev_in, s));
-        HIPCHK(e, hipStreamWaitEvent(c, e->ev_in, 0));
-    }
-    const int grid = (int)std::min<size_t>((m + PEEK_BLOCK - 1) / PEEK_BLOCK, (size_t)PEEK_GRID);
-    k_peek<<<grid, PEEK_BLOCK, 0, c>>>((uint64_t)m, a, e->d_cfg, (uint32_t)e->h_cfg.size(), e->d_tb, e->tb_cap - 1,
-                                       e->d_win, e->win_cap - 1, e->spill(), e->profile);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->ev_peek, c));
-    HIPCHK(e, hipStreamWaitEvent(s, e->ev_peek, 0));
-    return RL_OK;
-}
-
-// enqueue one batch of resets (rl_reset.h) of any size: k_reset_batch on
-// `chain`, where rl_reset_device puts its DEL -- after the replay of every
-// batch enqueued before, before that of every batch enqueued after; s waits
-// for it.  Nothing is counted in rl_stats and no error flag is raised.
-static int run_reset_batch(rl_engine* e, size_t m, const uint64_t* key, const int64_t* ts, const uint32_t* cfg,
-                           uint8_t* status, hipStream_t s, bool inputs_ready) {
-    if (m == 0) return RL_OK;
-    hipStream_t c = e->chain;
-    if (!inputs_ready) {
-        HIPCHK(e, hipEventRecord(e->ev_in, s));
-        HIPCHK(e, hipStreamWaitEvent(c, e->ev_in, 0));
-    }
-    const int grid = (int)std::min<size_t>((m + RESET_BLOCK - 1) / RESET_BLOCK, (size_t)RESET_GRID);
-    k_reset_batch<<<grid, RESET_BLOCK, 0, c>>>((uint64_t)m, key, ts, cfg, status, e->d_cfg, (uint32_t)e->h_cfg.size(),
-                                               e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1, e->spill());
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->ev_reset, c));
-    HIPCHK(e, hipStreamWaitEvent(s, e->ev_reset, 0));
-    return RL_OK;
-}
-
-// enqueue the peek or the reset step of the routed path (include/rl_route.h):
-// k_peek_routed / k_reset_routed on `chain`, ordered there like run_peek and
-// run_reset_batch -- after the replay of every decide batch and the DEL of
-// every reset enqueued before, before those enqueued after.  The kernel always
-// waits for s: the merge produced count, order and the store clocks there
-// (RL_OPT_PIPELINE promises the caller's arrays, not the router's).  Its end
-// is recorded into `done` when given, else so waits for it.  No buffer set is
-// taken, so m_max is not bounded by max_batch; nothing is counted in rl_stats;
-// the one flag it can raise is EF_ROUTED_OVER.
-static int run_routed_op(rl_engine* e, bool reset, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
-                         hipEvent_t done) {
-    hipStream_t c = e->chain;
-    HIPCHK(e, hipEventRecord(e->ev_in, s));
-    HIPCHK(e, hipStreamWaitEvent(c, e->ev_in, 0));
-    const uint32_t ncfg = (uint32_t)e->h_cfg.size();
-    if (reset) {
-        const int grid = (int)std::min<size_t>((m_max + RESET_BLOCK - 1) / RESET_BLOCK, (size_t)RESET_GRID);
-        k_reset_routed<<<grid, RESET_BLOCK, 0, c>>>((uint64_t)m_max, io, e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1,
-                                                    e->d_win, e->win_cap - 1, e->spill());
-    } else {
-        const int grid = (int)std::min<size_t>((m_max + PEEK_BLOCK - 1) / PEEK_BLOCK, (size_t)PEEK_GRID);
-        k_peek_routed<<<grid, PEEK_BLOCK, 0, c>>>((uint64_t)m_max, io, e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1,
-                                                  e->d_win, e->win_cap - 1, e->spill(), e->profile);
-    }
-    HIPCHK(e, hipGetLastError());
-    if (done) {
-        HIPCHK(e, hipEventRecord(done, c));
-    } else {
-        const hipEvent_t ev = reset ? e->ev_reset : e->ev_peek;
-        HIPCHK(e, hipEventRecord(ev, c));
-        HIPCHK(e, hipStreamWaitEvent(so, ev, 0));
-    }
-    return RL_OK;
-}
-
-// the C-ABI of both routed steps: argument checks as rl_decide_routed_device_io
-// / _ev, except that m_max is bounded by the 32-bit `order` only
-static int routed_op_entry(rl_engine* e, bool reset, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
-                           const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
-                           void* out_stream, void* done_event) {
-    if (!e || !count || (m_max && (!recv || !order || !server_ms || !res))) return RL_EINVAL;
-    if (m_max > (size_t)UINT32_MAX) return fail(e, RL_EINVAL, "routed batch bound above the 32-bit order index");
-    (void)hipSetDevice(e->device);
-    hipStream_t s = in_stream ? (hipStream_t)in_stream : e->stream;
-    if (!m_max) {   // nothing to run: the event marks the caller's stream
-        if (done_event) HIPCHK(e, hipEventRecord((hipEvent_t)done_event, s));
-        return RL_OK;
-    }
-    const RoutedIo io{recv, order, count, server_ms, res, e->d_eflags};
-    return run_routed_op(e, reset, m_max, io, s, out_stream ? (hipStream_t)out_stream : s, (hipEvent_t)done_event);
-}
-
 // Launch every kernel once at creation, on batches of requests that are all
 // rejected (no config is registered yet), so no table entry is touched: HIP
 // loads kernels lazily, and a server's first batch on either path (k_small, or
 // the big path when load grows) would otherwise stall its queue for the load.
 static int warm_up(rl_engine* e) {
+    const rl_stats fresh = e->stats;   // the warm-up batches are not counted
     const uint32_t mb = std::min<uint32_t>(e->max_batch, e->small_max + 1);
     hipStream_t s = e->stream;
     HIPCHK(e, hipMemsetAsync(e->d_key, 0, 8 * (size_t)mb, s));
@@ -1506,42 +1160,18 @@ static int warm_up(rl_engine* e) {
         // (mb <= up_max unless RL_UP_MAX says otherwise): zero-sized launches
         k_unpermute_routed<<<1, 256, GROUP_LDS, s>>>(nullptr, nullptr, 0u, e->invalid_key, e->d_cfg, ar, ri);
         k_unpermute<<<1, 256, GROUP_LDS, s>>>(nullptr, nullptr, 0u, e->invalid_key, e->d_cfg, a, a);
-        // the routed peek and reset steps, on the same empty batch: they read
-        // the zero count and nothing else
-        const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
-        for (const bool reset : {false, true}) {
-            const int rr = run_routed_op(e, reset, 1, io, s, s, nullptr);
-            if (rr != RL_OK) return rr;
-        }
     }
-    {   // the read-only query kernel
-        const int r = run_peek(e, 1, a, s, false);
-        if (r != RL_OK) return r;
-    }
-    {   // the batched Reset: no config is registered yet, so the request is rejected
-        const int r = run_reset_batch(e, 1, e->d_key, e->d_ts, e->d_cfgid, e->d_dec, s, false);
-        if (r != RL_OK) return r;
-    }
-    // the table count / GC / key listing kernels, on empty ranges: a server's
-    // first periodic count must not wait for their lazy load
-    k_table_count<<<1, 256, 0, s>>>(e->d_tb, 0, 0, e->profile, e->d_count);
-    k_table_count<<<1, 256, 0, s>>>(e->d_win, 0, 0, e->profile, e->d_count);
-    k_table_count<<<1, 256, 0, s>>>(e->d_spill, 0, 0, e->profile, e->d_count);
-    k_rehash<<<1, 256, 0, s>>>(e->d_tb, 0, e->d_tb, e->tb_cap - 1, 0, e->profile, e->d_count);
-    k_rehash<<<1, 256, 0, s>>>(e->d_win, 0, e->d_win, e->win_cap - 1, 0, e->profile, e->d_count);
-    k_spill_rehash<<<1, 256, 0, s>>>(e->d_spill, 0, e->d_spill, e->spill_cap - 1, e->d_win, e->win_cap - 1, 0,
-                                     e->profile, e->d_count);
-    HIPCHK(e, hipGetLastError());
-    const int r = drain(e);
+    // the other units' kernels, each unit its own
+    int r = ops_warm_up(e);
+    if (r == RL_OK) r = tables_warm_up(e);
+    if (r == RL_OK) r = drain(e);
     if (r != RL_OK) return r;
     HIPCHK(e, hipMemset(e->d_eflags, 0, 4));
     // the warm-up batches had no huge segment: without this, the first real
     // batches (all those enqueued before one replays) would take the light
     // kernel, which replays a hot key as one wave (~0.75 ms per 1M batch)
     *(volatile uint32_t*)e->h_huge = 1u;
-    e->stats = rl_stats{};
-    e->stats.sort_bits = e->sort_bits;
-    e->stats.sort_passes = e->sort_passes;
+    e->stats = fresh;
     return RL_OK;
 }
 
@@ -1621,18 +1251,6 @@ extern "C" int rl_decide_routed_device(rl_engine* e, size_t m_max, const uint32_
     return rl_decide_routed_device_io(e, m_max, count, recv, order, server_ms, res, stream, stream);
 }
 
-extern "C" int rl_peek_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
-                                     const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
-                                     void* in_stream, void* out_stream, void* done_event) {
-    return routed_op_entry(e, false, m_max, count, recv, order, server_ms, res, in_stream, out_stream, done_event);
-}
-
-extern "C" int rl_reset_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
-                                      const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
-                                      void* in_stream, void* out_stream, void* done_event) {
-    return routed_op_entry(e, true, m_max, count, recv, order, server_ms, res, in_stream, out_stream, done_event);
-}
-
 extern "C" int rl_decide_batch_keys_device(rl_engine* e, size_t m, const uint8_t* key_bytes, uint64_t nbytes,
                                            const uint64_t* key_offsets, uint64_t seed, const char* prefix,
                                            size_t prefix_len, const int64_t* ts_ns, const int64_t* n,
@@ -1668,551 +1286,17 @@ extern "C" int rl_decide_batch(rl_engine* e, size_t m, const uint64_t* key_id, c
     HIPCHK(e, hipMemsetAsync(e->d_eflags, 0, 4, s));
     for (size_t off = 0; off < m; off += e->max_batch) {
         uint32_t c = (uint32_t)std::min<size_t>(e->max_batch, m - off);
-        HIPCHK(e, hipMemcpyAsync(e->d_key, key_id + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_ts, ts_ns + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_n, n + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_cfgid, cfg_id + off, 4 * (size_t)c, hipMemcpyHostToDevice, s));
-        if (server_ms) HIPCHK(e, hipMemcpyAsync(e->d_sms, server_ms + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
+        int r = stage_in(e, off, c, key_id, ts_ns, n, cfg_id, server_ms, s);
         ReqArgs a{e->d_key, e->d_ts, e->d_n, e->d_cfgid, server_ms ? e->d_sms : nullptr,
                   e->d_dec, e->d_rem, e->d_retry, e->d_reset, tokens ? e->d_tok : nullptr};
-        int r = run_batch(e, c, a, s, false);
+        if (r == RL_OK) r = run_batch(e, c, a, s, false);
+        if (r == RL_OK) r = stage_out(e, off, c, decision, remaining, retry_after_ns, reset_at_ns, tokens, s);
         if (r != RL_OK) return r;
-        HIPCHK(e, hipMemcpyAsync(decision + off, e->d_dec, c, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipMemcpyAsync(remaining + off, e->d_rem, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipMemcpyAsync(retry_after_ns + off, e->d_retry, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipMemcpyAsync(reset_at_ns + off, e->d_reset, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
-        if (tokens) HIPCHK(e, hipMemcpyAsync(tokens + off, e->d_tok, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
         HIPCHK(e, hipStreamSynchronize(s));
     }
     uint32_t f = 0;
     HIPCHK(e, hipMemcpy(&f, e->d_eflags, 4, hipMemcpyDeviceToHost));
     return check_flags(e, f);
-}
-
-// The DEL only writes `when` fields of table entries, which only the replays
-// (k_tb_chain, k_small: both on `chain`) read; the grouping reads entry keys
-// only and the finish no table state.  So one kernel on `chain` between two
-// replays is exactly "after every earlier batch, before every later one".
-extern "C" int rl_reset_device(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns, void* stream) {
-    if (!e || cfg_id >= e->h_cfg.size() || key_id == EMPTY_KEY) return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    k_reset<<<1, 1, 0, e->chain>>>(key_id, ts_ns, e->d_cfg, cfg_id, e->d_tb, e->tb_cap - 1, e->d_win,
-                                    e->win_cap - 1, e->spill());
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->ev_reset, e->chain));
-    HIPCHK(e, hipStreamWaitEvent(s, e->ev_reset, 0));
-    return RL_OK;
-}
-
-extern "C" int rl_reset(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns) {
-    const int r = rl_reset_device(e, cfg_id, key_id, ts_ns, nullptr);
-    if (r != RL_OK) return r;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return RL_OK;
-}
-
-// Many resets in one launch (rl_reset.h), ordered as rl_reset_device.  The
-// grid strides over any m: no chunking on the device entry point.
-extern "C" int rl_reset_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
-                                     const uint32_t* cfg_id, uint8_t* status, void* stream) {
-    if (!e || (m && (!key_id || !ts_ns || !cfg_id))) return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    return run_reset_batch(e, m, key_id, ts_ns, cfg_id, status, s, (e->flags & RL_OPT_PIPELINE) != 0);
-}
-
-extern "C" int rl_reset_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
-                              const uint32_t* cfg_id, uint8_t* status) {
-    if (!e || (m && (!key_id || !ts_ns || !cfg_id))) return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    hipStream_t s = e->stream;
-    // chunks of max_batch: the size of the host API's staging arrays
-    for (size_t off = 0; off < m; off += e->max_batch) {
-        const uint32_t c = (uint32_t)std::min<size_t>(e->max_batch, m - off);
-        HIPCHK(e, hipMemcpyAsync(e->d_key, key_id + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_ts, ts_ns + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_cfgid, cfg_id + off, 4 * (size_t)c, hipMemcpyHostToDevice, s));
-        // the staged inputs arrive on s: the kernel always waits for them
-        const int r = run_reset_batch(e, c, e->d_key, e->d_ts, e->d_cfgid, status ? e->d_dec : nullptr, s, false);
-        if (r != RL_OK) return r;
-        if (status) HIPCHK(e, hipMemcpyAsync(status + off, e->d_dec, c, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipStreamSynchronize(s));
-    }
-    return RL_OK;
-}
-
-extern "C" int rl_reset_grid_cap(void) { return RESET_GRID * RESET_BLOCK; }
-
-// Usage tally (rl_tally.h).  k_tally runs on the caller's stream, behind the
-// finish of the batch it counts; it touches the tally's own memory only, so it
-// needs no order against the engine's streams.  What must wait for it -- a read,
-// a clear, a new config's row, destroy -- waits for the event recorded behind
-// the last tally of every stream one was enqueued on (drain()).
-static int run_tally(rl_engine* e, size_t m, const uint64_t* key, const uint32_t* cfg, const int64_t* n,
-                     const uint8_t* dec, hipStream_t s) {
-    hipEvent_t ev = nullptr;
-    for (auto& se : e->tally_ev)
-        if (se.first == s) ev = se.second;
-    if (!ev) {
-        if (e->tally_ev.size() >= 16) {   // streams come and go: keep the list short
-            for (auto& se : e->tally_ev) {
-                HIPCHK(e, hipEventSynchronize(se.second));
-                (void)hipEventDestroy(se.second);
-            }
-            e->tally_ev.clear();
-        }
-        HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        e->tally_ev.emplace_back(s, ev);
-    }
-    HIPCHK(e, tally_launch((uint64_t)m, key, cfg, n, dec, (uint32_t)e->h_cfg.size(), e->d_tally_cfg, e->d_tally_glob,
-                           e->d_tally_keys, e->tally_slots, s));
-    HIPCHK(e, hipEventRecord(ev, s));
-    e->tally_batches++;
-    e->tally_requests += m;
-    return RL_OK;
-}
-
-extern "C" int rl_tally_enable(rl_engine* e, const rl_tally_opts* o) {
-    if (!e || !o || o->struct_size != sizeof(rl_tally_opts) || e->tally_on) return RL_EINVAL;
-    if (o->key_slots > (1u << 24)) return fail(e, RL_EINVAL, "tally key_slots above 1 << 24");
-    (void)hipSetDevice(e->device);
-    const uint64_t slots = pow2_at_least(std::max<uint64_t>(o->key_slots ? o->key_slots : 65536, 16));
-    const uint32_t cap = std::max<uint32_t>(64, (uint32_t)pow2_at_least(e->h_cfg.size() + 1));
-    bool ok = hipMalloc(&e->d_tally_keys, sizeof(TallyKey) * slots) == hipSuccess;
-    ok = ok && hipMalloc(&e->d_tally_cfg, sizeof(tally_u64) * TALLY_CFG_WORDS * cap) == hipSuccess;
-    ok = ok && hipMalloc(&e->d_tally_glob, sizeof(tally_u64) * TG_WORDS) == hipSuccess;
-    if (ok) {
-        ok = tally_clear_launch(e->d_tally_keys, slots, e->d_tally_cfg, (uint64_t)TALLY_CFG_WORDS * cap,
-                                e->d_tally_glob, e->stream) == hipSuccess;
-        // an empty launch loads the kernel now, not in front of the first batch
-        ok = ok && tally_launch(0, nullptr, nullptr, nullptr, nullptr, 0, e->d_tally_cfg, e->d_tally_glob,
-                                e->d_tally_keys, slots, e->stream) == hipSuccess;
-        ok = ok && hipStreamSynchronize(e->stream) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipFree(e->d_tally_keys); (void)hipFree(e->d_tally_cfg); (void)hipFree(e->d_tally_glob);
-        e->d_tally_keys = nullptr; e->d_tally_cfg = nullptr; e->d_tally_glob = nullptr;
-        return fail(e, RL_ENOMEM, "tally allocation failed");
-    }
-    e->tally_slots = slots;
-    e->tally_cfg_cap = cap;
-    e->tally_batches = e->tally_requests = 0;
-    e->tally_on = true;
-    return RL_OK;
-}
-
-extern "C" int rl_tally_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const uint32_t* cfg_id,
-                                     const int64_t* n, const uint8_t* decision, void* stream) {
-    if (!e || !e->tally_on || (m && (!key_id || !cfg_id || !n || !decision))) return RL_EINVAL;
-    if (m == 0) return RL_OK;
-    (void)hipSetDevice(e->device);
-    return run_tally(e, m, key_id, cfg_id, n, decision, stream ? (hipStream_t)stream : e->stream);
-}
-
-extern "C" int rl_tally_batch(rl_engine* e, size_t m, const uint64_t* key_id, const uint32_t* cfg_id,
-                              const int64_t* n, const uint8_t* decision) {
-    if (!e || !e->tally_on || (m && (!key_id || !cfg_id || !n || !decision))) return RL_EINVAL;
-    if (m == 0) return RL_OK;
-    (void)hipSetDevice(e->device);
-    hipStream_t s = e->stream;
-    const uint64_t b0 = e->tally_batches;
-    // chunks of max_batch: the size of the host API's staging arrays
-    for (size_t off = 0; off < m; off += e->max_batch) {
-        const uint32_t c = (uint32_t)std::min<size_t>(e->max_batch, m - off);
-        HIPCHK(e, hipMemcpyAsync(e->d_key, key_id + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_cfgid, cfg_id + off, 4 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_n, n + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_dec, decision + off, c, hipMemcpyHostToDevice, s));
-        const int r = run_tally(e, c, e->d_key, e->d_cfgid, e->d_n, e->d_dec, s);
-        if (r != RL_OK) return r;
-        HIPCHK(e, hipStreamSynchronize(s));
-    }
-    e->tally_batches = b0 + 1;   // one call, one batch, however many chunks
-    return RL_OK;
-}
-
-extern "C" int rl_tally_read(rl_engine* e, rl_tally_cfg* cfg_out, size_t cfg_cap, uint32_t* ncfg,
-                             rl_tally_key* key_out, size_t key_cap, uint64_t* keys_tracked, rl_tally_info* info,
-                             int clear) {
-    if (!e || !e->tally_on) return RL_EINVAL;
-    if (info && info->struct_size < 8) return RL_EINVAL;
-    static_assert(sizeof(rl_tally_cfg) == sizeof(tally_u64) * TALLY_CFG_WORDS, "rl_tally_cfg is a counter row");
-    static_assert(sizeof(rl_tally_key) == sizeof(TallyKey), "rl_tally_key is a table record");
-    (void)hipSetDevice(e->device);
-    for (auto& se : e->tally_ev) HIPCHK(e, hipEventSynchronize(se.second));
-    hipStream_t s = e->stream;
-    const uint32_t nc = (uint32_t)e->h_cfg.size();
-    tally_u64 glob[TG_WORDS];
-    HIPCHK(e, hipMemcpyAsync(glob, e->d_tally_glob, sizeof(glob), hipMemcpyDeviceToHost, s));
-    const size_t rows = cfg_out ? std::min<size_t>(cfg_cap, nc) : 0;
-    if (rows) HIPCHK(e, hipMemcpyAsync(cfg_out, e->d_tally_cfg, sizeof(rl_tally_cfg) * rows, hipMemcpyDeviceToHost, s));
-    std::vector<rl_tally_key> tab;
-    if (key_out && key_cap) {
-        tab.resize(e->tally_slots);
-        HIPCHK(e, hipMemcpyAsync(tab.data(), e->d_tally_keys, sizeof(rl_tally_key) * e->tally_slots,
-                                 hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(e, hipStreamSynchronize(s));
-    if (!tab.empty()) {
-        // the top keys, selected on the host from the copy
-        auto end = std::remove_if(tab.begin(), tab.end(), [](const rl_tally_key& r) { return r.key_id == EMPTY_KEY; });
-        const size_t want = std::min<size_t>(key_cap, (size_t)(end - tab.begin()));
-        std::partial_sort(tab.begin(), tab.begin() + want, end, [](const rl_tally_key& a, const rl_tally_key& b) {
-            return a.denied != b.denied ? a.denied > b.denied : a.key_id < b.key_id;
-        });
-        memcpy(key_out, tab.data(), sizeof(rl_tally_key) * want);
-    }
-    if (ncfg) *ncfg = nc;
-    if (keys_tracked) *keys_tracked = glob[TG_KEYS];
-    if (info) {
-        rl_tally_info I{};
-        I.key_slots = e->tally_slots;
-        I.keys_tracked = glob[TG_KEYS];
-        I.untracked_requests = glob[TG_UNTRACKED_REQ];
-        I.untracked_units = glob[TG_UNTRACKED_UNITS];
-        I.unknown_cfg = glob[TG_UNKNOWN];
-        I.bad_codes = glob[TG_BAD];
-        I.batches = e->tally_batches;
-        I.requests = e->tally_requests;
-        const int r = copy_out(info, I);
-        if (r != RL_OK) return r;
-    }
-    if (clear) {
-        HIPCHK(e, tally_clear_launch(e->d_tally_keys, e->tally_slots, e->d_tally_cfg,
-                                     (uint64_t)TALLY_CFG_WORDS * e->tally_cfg_cap, e->d_tally_glob, s));
-        HIPCHK(e, hipStreamSynchronize(s));
-        e->tally_batches = e->tally_requests = 0;
-    }
-    return RL_OK;
-}
-
-extern "C" int rl_tally_grid_cap(void) { return TALLY_GRID * TALLY_BLOCK; }
-
-// Read-only queries (rl_peek.h).  Ordering as rl_reset_device: one kernel on
-// `chain` is after every batch enqueued before the call and before every one
-// enqueued after it.  It raises no error flag, so the sticky status of
-// rl_engine_sync never comes from a peek.
-extern "C" int rl_peek_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
-                                    const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
-                                    uint8_t* decision, int64_t* remaining, int64_t* retry_after_ns,
-                                    int64_t* reset_at_ns, double* tokens, void* stream) {
-    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !decision || !remaining || !retry_after_ns || !reset_at_ns)))
-        return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    // the grid strides over any m: no chunking
-    ReqArgs a{key_id, ts_ns, n, cfg_id, server_ms, decision, remaining, retry_after_ns, reset_at_ns, tokens};
-    return run_peek(e, m, a, s, (e->flags & RL_OPT_PIPELINE) != 0);
-}
-
-extern "C" int rl_peek_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
-                             const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* decision,
-                             int64_t* remaining, int64_t* retry_after_ns, int64_t* reset_at_ns, double* tokens) {
-    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !decision || !remaining || !retry_after_ns || !reset_at_ns)))
-        return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    hipStream_t s = e->stream;
-    // chunks of max_batch: the size of the host API's staging arrays
-    for (size_t off = 0; off < m; off += e->max_batch) {
-        uint32_t c = (uint32_t)std::min<size_t>(e->max_batch, m - off);
-        HIPCHK(e, hipMemcpyAsync(e->d_key, key_id + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_ts, ts_ns + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_n, n + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(e->d_cfgid, cfg_id + off, 4 * (size_t)c, hipMemcpyHostToDevice, s));
-        if (server_ms) HIPCHK(e, hipMemcpyAsync(e->d_sms, server_ms + off, 8 * (size_t)c, hipMemcpyHostToDevice, s));
-        ReqArgs a{e->d_key, e->d_ts, e->d_n, e->d_cfgid, server_ms ? e->d_sms : nullptr,
-                  e->d_dec, e->d_rem, e->d_retry, e->d_reset, tokens ? e->d_tok : nullptr};
-        // the staged inputs arrive on s: the kernel always waits for them
-        int r = run_peek(e, c, a, s, false);
-        if (r != RL_OK) return r;
-        HIPCHK(e, hipMemcpyAsync(decision + off, e->d_dec, c, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipMemcpyAsync(remaining + off, e->d_rem, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipMemcpyAsync(retry_after_ns + off, e->d_retry, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipMemcpyAsync(reset_at_ns + off, e->d_reset, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
-        if (tokens) HIPCHK(e, hipMemcpyAsync(tokens + off, e->d_tok, 8 * (size_t)c, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipStreamSynchronize(s));
-    }
-    return RL_OK;
-}
-
-extern "C" int rl_peek_grid_cap(void) { return PEEK_GRID * PEEK_BLOCK; }
-
-extern "C" int rl_table_info_get(rl_engine* e, int64_t now_ms, rl_table_info* out) {
-    if (!e || !out || out->struct_size < 8) return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    int r = drain(e);
-    if (r != RL_OK) return r;
-    // preallocated counters (no hipMalloc / hipFree, which synchronize the
-    // device, on a server's periodic count)
-    unsigned long long* d = e->d_count;
-    unsigned long long* h = e->h_count;
-    hipStream_t s = e->stream;
-    bool ok = hipMemsetAsync(d, 0, 6 * sizeof(unsigned long long), s) == hipSuccess;
-    k_table_count<<<1024, 256, 0, s>>>(e->d_tb, e->tb_cap, now_ms, e->profile, d);
-    k_table_count<<<1024, 256, 0, s>>>(e->d_win, e->win_cap, now_ms, e->profile, d + 2);
-    k_table_count<<<1024, 256, 0, s>>>(e->d_spill, e->spill_cap, now_ms, e->profile, d + 4);
-    ok = ok && hipMemcpyAsync(h, d, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) == hipSuccess;
-    ok = ok && hipStreamSynchronize(s) == hipSuccess;
-    if (!ok) return fail(e, RL_EDEVICE, "table count failed");
-    return copy_out(out, rl_table_info{sizeof(rl_table_info), 0, e->tb_cap, h[0], h[1], e->win_cap, h[2], h[3],
-                                       e->spill_cap, h[4], h[5]});
-}
-
-extern "C" int rl_table_keys(rl_engine* e, int64_t now_ms, rl_key_rec* out, size_t cap, uint64_t* count) {
-    if (!e || !count || (cap && !out)) return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    int r = drain(e);
-    if (r != RL_OK) return r;
-    unsigned long long* d = nullptr;
-    rl_key_rec* dout = nullptr;
-    HIPCHK(e, hipMalloc(&d, sizeof(unsigned long long)));
-    if (cap && hipMalloc(&dout, sizeof(rl_key_rec) * cap) != hipSuccess) {
-        (void)hipFree(d);
-        return fail(e, RL_ENOMEM, "table keys: allocation failed");
-    }
-    hipStream_t s = e->stream;
-    unsigned long long n = 0;
-    bool ok = hipMemsetAsync(d, 0, sizeof n, s) == hipSuccess;
-    k_table_keys<<<1024, 256, 0, s>>>(e->d_tb, e->tb_cap, e->d_win, e->win_cap, e->d_spill, e->spill_cap, now_ms,
-                                       e->profile, dout, cap, d);
-    ok = ok && hipMemcpyAsync(&n, d, sizeof n, hipMemcpyDeviceToHost, s) == hipSuccess;
-    ok = ok && hipStreamSynchronize(s) == hipSuccess;
-    if (ok && cap && n)
-        ok = hipMemcpy(out, dout, sizeof(rl_key_rec) * std::min<uint64_t>(n, cap), hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d);
-    (void)hipFree(dout);
-    if (!ok) return fail(e, RL_EDEVICE, "table keys failed");
-    *count = n;
-    return RL_OK;
-}
-
-// A table rebuild: fresh tables that receive the live state and then replace
-// the engine's.  rl_table_gc and rl_snapshot_import share every step, so what
-// follows the capacities (slot ids, sort bits) cannot drift between them.
-struct Rebuild {
-    TbEntry* tb = nullptr;
-    WinEntry* win = nullptr;
-    SpillEntry* sp = nullptr;
-    uint64_t tb_cap = 0, win_cap = 0, spill_cap = 0;
-    // [0..5] the engine's own tables (live, lost per table); from REBUILD_IMPORT
-    // on, four words per imported section (rl_snapshot.h SNAP_LIVE..)
-    unsigned long long* d = nullptr;
-};
-constexpr int REBUILD_IMPORT = 6;
-constexpr int REBUILD_WORDS = REBUILD_IMPORT + 3 * 4;
-
-static void rebuild_abort(Rebuild& R) {
-    (void)hipFree(R.tb);
-    (void)hipFree(R.win);
-    (void)hipFree(R.sp);
-    (void)hipFree(R.d);
-    R = Rebuild{};
-}
-
-// capacities (0 = keep; rounding and limits), drain, allocate and initialise
-// the fresh tables, and enqueue the rehash of the engine's live state at
-// now_ms on the engine's stream (not waited for)
-static int rebuild_begin(rl_engine* e, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity, Rebuild& R,
-                         const char* what) {
-    R.tb_cap = tb_capacity ? pow2_at_least(std::max<uint64_t>(tb_capacity, 1024)) : e->tb_cap;
-    R.win_cap = win_capacity ? pow2_at_least(std::max<uint64_t>(win_capacity, 1024)) : e->win_cap;
-    R.spill_cap = e->spill_follows ? pow2_at_least(std::max<uint64_t>(2 * R.win_cap, 1024)) : e->spill_cap;
-    if (R.tb_cap + R.win_cap >= (1ull << 31)) return fail(e, RL_EINVAL, "table capacities too large");
-    int r = drain(e);
-    if (r != RL_OK) return r;
-    bool ok = hipMalloc(&R.tb, sizeof(TbEntry) * R.tb_cap) == hipSuccess;
-    ok = ok && hipMalloc(&R.win, sizeof(WinEntry) * R.win_cap) == hipSuccess;
-    ok = ok && hipMalloc(&R.sp, sizeof(SpillEntry) * R.spill_cap) == hipSuccess;
-    ok = ok && hipMalloc(&R.d, REBUILD_WORDS * sizeof(unsigned long long)) == hipSuccess;
-    if (!ok) {
-        rebuild_abort(R);
-        return fail(e, RL_ENOMEM, std::string(what) + ": allocation failed");
-    }
-    hipStream_t s = e->stream;
-    k_init_tb<<<2048, 256, 0, s>>>(R.tb, R.tb_cap);
-    k_init_win<<<2048, 256, 0, s>>>(R.win, R.win_cap);
-    k_init_spill<<<2048, 256, 0, s>>>(R.sp, R.spill_cap);
-    if (hipMemsetAsync(R.d, 0, REBUILD_WORDS * sizeof(unsigned long long), s) != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        rebuild_abort(R);
-        return fail(e, RL_EDEVICE, std::string(what) + " failed");
-    }
-    k_rehash<<<2048, 256, 0, s>>>(e->d_tb, e->tb_cap, R.tb, R.tb_cap - 1, now_ms, e->profile, R.d);
-    k_rehash<<<2048, 256, 0, s>>>(e->d_win, e->win_cap, R.win, R.win_cap - 1, now_ms, e->profile, R.d + 2);
-    // after the window entries: each live spill entry is counted in its new entry
-    k_spill_rehash<<<2048, 256, 0, s>>>(e->d_spill, e->spill_cap, R.sp, R.spill_cap - 1, R.win, R.win_cap - 1, now_ms,
-                                        e->profile, R.d + 4);
-    return RL_OK;
-}
-
-// wait for the rebuild's kernels and read its counters
-static bool rebuild_finish(rl_engine* e, Rebuild& R, unsigned long long (&h)[REBUILD_WORDS]) {
-    hipStream_t s = e->stream;
-    bool ok = hipMemcpyAsync(h, R.d, sizeof h, hipMemcpyDeviceToHost, s) == hipSuccess;
-    ok = hipStreamSynchronize(s) == hipSuccess && ok;
-    return ok;
-}
-
-// the fresh tables become the engine's
-static void rebuild_commit(rl_engine* e, Rebuild& R) {
-    (void)hipFree(e->d_tb);
-    (void)hipFree(e->d_win);
-    (void)hipFree(e->d_spill);
-    (void)hipFree(R.d);
-    e->d_tb = R.tb;
-    e->d_win = R.win;
-    e->d_spill = R.sp;
-    // slot ids (the sort keys) follow the capacities
-    e->tb_cap = R.tb_cap;
-    e->win_cap = R.win_cap;
-    e->spill_cap = R.spill_cap;
-    e->win_base = (uint32_t)R.tb_cap;
-    e->invalid_key = (uint32_t)(R.tb_cap + R.win_cap);
-    e->sort_bits = bitlen(e->invalid_key);
-    e->sort_passes = (e->sort_bits + 7) / 8;
-    e->sort_shifts = sort_shifts(e->sort_bits, e->sort_passes);
-    e->stats.sort_bits = e->sort_bits;
-    e->stats.sort_passes = e->sort_passes;
-    R = Rebuild{};
-}
-
-extern "C" int rl_table_gc(rl_engine* e, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
-                           rl_table_info* out) {
-    if (!e || (out && out->struct_size < 8)) return RL_EINVAL;
-    (void)hipSetDevice(e->device);
-    Rebuild R;
-    int r = rebuild_begin(e, now_ms, tb_capacity, win_capacity, R, "table gc");
-    if (r != RL_OK) return r;
-    unsigned long long h[REBUILD_WORDS];
-    const bool ok = rebuild_finish(e, R, h);
-    if (!ok || h[1] || h[3] || h[5]) {
-        rebuild_abort(R);
-        return ok ? fail(e, RL_ENOMEM, "table gc: live keys do not fit the requested capacity")
-                  : fail(e, RL_EDEVICE, "table gc failed");
-    }
-    rebuild_commit(e, R);
-    return out ? rl_table_info_get(e, now_ms, out) : RL_OK;
-}
-
-// ---------------------------------------------------------------------------
-// snapshots (include/rl_snapshot.h)
-// ---------------------------------------------------------------------------
-
-static rl_snapshot_info snapshot_info_of(const SnapHeader& h) {
-    return rl_snapshot_info{sizeof(rl_snapshot_info), h.version, h.profile, h.world, h.rank, 0, h.now_ms,
-                            h.tb_count, h.win_count, h.spill_count, h.total, h.payload_sum};
-}
-
-extern "C" int rl_snapshot_inspect(const void* buf, size_t len, rl_snapshot_info* out) {
-    if (!out || out->struct_size < 8) return RL_EINVAL;
-    SnapHeader h;
-    if (!snap_header_ok(buf, len, &h) || !snap_payload_ok(buf, h)) return RL_EINVAL;
-    return copy_out(out, snapshot_info_of(h));
-}
-
-extern "C" int rl_snapshot_export(rl_engine* e, int64_t now_ms, uint32_t world, uint32_t rank, void* buf, size_t cap,
-                                  rl_snapshot_info* out) {
-    if (!e || !out || out->struct_size < 8 || (!buf && cap)) return RL_EINVAL;
-    if (world == 0 || rank >= world) return fail(e, RL_EINVAL, "snapshot export: rank outside the world");
-    (void)hipSetDevice(e->device);
-    int r = drain(e);
-    if (r != RL_OK) return r;
-    hipStream_t s = e->stream;
-    unsigned long long* d = e->d_count;
-    unsigned long long* h = e->h_count;
-    // the live size first (count and checksum, no writes): nothing runs on
-    // the drained engine, so the writing launch finds the same records
-    bool ok = hipMemsetAsync(d, 0, SNAP_WORDS * sizeof(unsigned long long), s) == hipSuccess;
-    k_snapshot_export<false><<<2048, SNAP_BLOCK, 0, s>>>(e->d_tb, e->tb_cap, e->d_win, e->win_cap, e->d_spill,
-                                                         e->spill_cap, now_ms, e->profile, world, rank, nullptr, 0,
-                                                         nullptr, 0, nullptr, 0, d);
-    ok = ok && hipMemcpyAsync(h, d, SNAP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) == hipSuccess;
-    ok = ok && hipStreamSynchronize(s) == hipSuccess;
-    if (!ok) return fail(e, RL_EDEVICE, "snapshot export: count failed");
-    const SnapHeader hd = snap_make_header(e->profile, h[SNAP_TB], h[SNAP_WIN], h[SNAP_SPILL], now_ms, world, rank,
-                                           h[SNAP_SUM]);
-    r = copy_out(out, snapshot_info_of(hd));
-    if (r != RL_OK || !buf) return r;
-    if (cap < hd.total) return fail(e, RL_ENOMEM, "snapshot export: buffer too small");
-    const size_t payload = hd.total - sizeof hd;
-    if (payload) {
-        uint8_t* stage = nullptr;
-        if (hipMalloc(&stage, payload) != hipSuccess) return fail(e, RL_ENOMEM, "snapshot export: allocation failed");
-        const size_t tb_end = hd.tb_off + sizeof(TbEntry) * hd.tb_count;
-        ok = hipMemsetAsync(d, 0, SNAP_WORDS * sizeof(unsigned long long), s) == hipSuccess;
-        if (hd.win_off > tb_end)   // the padding in front of the window section
-            ok = ok && hipMemsetAsync(stage + (tb_end - sizeof hd), 0, hd.win_off - tb_end, s) == hipSuccess;
-        k_snapshot_export<true><<<2048, SNAP_BLOCK, 0, s>>>(
-            e->d_tb, e->tb_cap, e->d_win, e->win_cap, e->d_spill, e->spill_cap, now_ms, e->profile, world, rank,
-            (TbEntry*)(stage + (hd.tb_off - sizeof hd)), hd.tb_count, (WinEntry*)(stage + (hd.win_off - sizeof hd)),
-            hd.win_count, (SpillEntry*)(stage + (hd.spill_off - sizeof hd)), hd.spill_count, d);
-        ok = ok && hipMemcpyAsync(h, d, SNAP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) == hipSuccess;
-        ok = ok && hipStreamSynchronize(s) == hipSuccess;
-        ok = ok && h[SNAP_TB] == hd.tb_count && h[SNAP_WIN] == hd.win_count && h[SNAP_SPILL] == hd.spill_count &&
-             h[SNAP_SUM] == hd.payload_sum;
-        ok = ok && hipMemcpy((uint8_t*)buf + sizeof hd, stage, payload, hipMemcpyDeviceToHost) == hipSuccess;
-        (void)hipFree(stage);
-        if (!ok) return fail(e, RL_EDEVICE, "snapshot export failed");
-    }
-    memcpy(buf, &hd, sizeof hd);
-    return RL_OK;
-}
-
-extern "C" int rl_snapshot_import(rl_engine* e, const void* buf, size_t len, int64_t now_ms, uint64_t tb_capacity,
-                                  uint64_t win_capacity, rl_table_info* out) {
-    if (!e || (out && out->struct_size < 8)) return RL_EINVAL;
-    SnapHeader hd;
-    if (!snap_header_ok(buf, len, &hd)) return fail(e, RL_EINVAL, "snapshot import: bad header");
-    if (hd.profile != e->profile) return fail(e, RL_EINVAL, "snapshot import: taken under the other profile");
-    (void)hipSetDevice(e->device);
-    const size_t payload = hd.total - sizeof hd;
-    uint8_t* stage = nullptr;
-    if (payload && hipMalloc(&stage, payload) != hipSuccess)
-        return fail(e, RL_ENOMEM, "snapshot import: allocation failed");
-    Rebuild R;
-    int r = rebuild_begin(e, now_ms, tb_capacity, win_capacity, R, "snapshot import");
-    if (r != RL_OK) {
-        (void)hipFree(stage);
-        return r;
-    }
-    hipStream_t s = e->stream;
-    bool ok = !payload || hipMemcpyAsync(stage, (const uint8_t*)buf + sizeof hd, payload, hipMemcpyHostToDevice, s) ==
-                              hipSuccess;
-    if (ok) {
-        unsigned long long* c = R.d + REBUILD_IMPORT;
-        k_snapshot_import<<<2048, SNAP_BLOCK, 0, s>>>((const TbEntry*)(stage + (hd.tb_off - sizeof hd)), hd.tb_count,
-                                                      R.tb, R.tb_cap - 1, now_ms, e->profile,
-                                                      (uint64_t)RL_SNAPSHOT_TAG_TB, c);
-        k_snapshot_import<<<2048, SNAP_BLOCK, 0, s>>>((const WinEntry*)(stage + (hd.win_off - sizeof hd)),
-                                                      hd.win_count, R.win, R.win_cap - 1, now_ms, e->profile,
-                                                      (uint64_t)RL_SNAPSHOT_TAG_WIN, c + 4);
-        // after the window section: a spill record is counted in its user key's new entry
-        k_snapshot_import_spill<<<2048, SNAP_BLOCK, 0, s>>>((const SpillEntry*)(stage + (hd.spill_off - sizeof hd)),
-                                                            hd.spill_count, R.sp, R.spill_cap - 1, R.win,
-                                                            R.win_cap - 1, now_ms, e->profile, c + 8);
-    }
-    unsigned long long h[REBUILD_WORDS];
-    ok = rebuild_finish(e, R, h) && ok;
-    (void)hipFree(stage);
-    const unsigned long long* c = h + REBUILD_IMPORT;
-    int code = RL_OK;
-    const char* msg = "";
-    if (!ok) {
-        code = RL_EDEVICE, msg = "snapshot import failed";
-    } else if (c[SNAP_CHECK] + c[4 + SNAP_CHECK] + c[8 + SNAP_CHECK] != hd.payload_sum) {
-        code = RL_EINVAL, msg = "snapshot import: payload checksum mismatch";
-    } else if (c[SNAP_CONFLICT] || c[4 + SNAP_CONFLICT]) {
-        code = RL_EEXIST, msg = "snapshot import: a key is in the engine and in the snapshot";
-    } else if (h[1] || h[3] || h[5] || c[SNAP_LOST] || c[4 + SNAP_LOST] || c[8 + SNAP_LOST]) {
-        code = RL_ENOMEM, msg = "snapshot import: live keys do not fit the requested capacity";
-    }
-    if (code != RL_OK) {
-        rebuild_abort(R);
-        return fail(e, code, msg);
-    }
-    rebuild_commit(e, R);
-    return out ? rl_table_info_get(e, now_ms, out) : RL_OK;
 }
 
 extern "C" int rl_engine_stats(rl_engine* e, rl_stats* out) {
@@ -2291,9 +1375,12 @@ extern "C" int rl_engine_debug_q14_slow(rl_engine* e, uint64_t* out) {
     (void)hipSetDevice(e->device);
     int r = drain(e);
     if (r != RL_OK) return r;
-    unsigned long long v = 0;
+    // the counter is per code object: the decision kernels' here, the peeks' in rl_ops.hip
+    unsigned long long v = 0, w = 0;
     HIPCHK(e, hipMemcpyFromSymbol(&v, HIP_SYMBOL(rlq::q14_slow_calls), sizeof v, 0, hipMemcpyDeviceToHost));
-    *out = v;
+    r = ops_q14_slow(e, &w);
+    if (r != RL_OK) return r;
+    *out = v + w;
     return RL_OK;
 }
 

@@ -1,0 +1,205 @@
+// rl_ops.hip -- Peek and Reset (single, batched, routed): the kernels of
+// rl_peek.h and rl_reset.h and their C entry points.  Each is one kernel on
+// the engine's `chain` stream between two replays (chain_op, rl_engine_impl.h).
+// A code object of its own: that of the decision kernels (rl_engine.hip) does
+// not change with it.
+#include <hip/hip_runtime.h>
+
+#include "../../include/rl_engine.h"
+#include "../../include/rl_route.h"
+#include "rl_engine_impl.h"
+#include "rl_peek.h"
+#include "rl_reset.h"
+
+using namespace rl;
+
+// Reset of one key (rl_reset_device): the arguments by value, one thread
+__global__ void k_reset(uint64_t key, int64_t ts, const CfgDev* cfgs, uint32_t cfg, TbEntry* tb,
+                        uint64_t tb_mask, WinEntry* win, uint64_t win_mask, Spill spill) {
+    reset_one(key, &ts, cfgs[cfg], tb, tb_mask, win, win_mask, spill);
+}
+
+// enqueue one read-only query batch (rl_peek.h) of any size: k_peek as a
+// chain op; s waits for it.  No per-batch buffer is involved, and nothing is
+// counted in rl_stats.
+static int run_peek(rl_engine* e, size_t m, ReqArgs a, hipStream_t s, bool inputs_ready) {
+    if (m == 0) return RL_OK;
+    return chain_op(e, s, inputs_ready, s, e->ev_peek, nullptr, [&](hipStream_t c) {
+        k_peek<<<grid_for(m, PEEK_BLOCK, PEEK_GRID), PEEK_BLOCK, 0, c>>>(
+            (uint64_t)m, a, e->d_cfg, (uint32_t)e->h_cfg.size(), e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1,
+            e->spill(), e->profile);
+    });
+}
+
+// enqueue one batch of resets (rl_reset.h) of any size: k_reset_batch as a
+// chain op, where rl_reset_device puts its DEL; s waits for it.  Nothing is
+// counted in rl_stats and no error flag is raised.
+static int run_reset_batch(rl_engine* e, size_t m, const uint64_t* key, const int64_t* ts, const uint32_t* cfg,
+                           uint8_t* status, hipStream_t s, bool inputs_ready) {
+    if (m == 0) return RL_OK;
+    return chain_op(e, s, inputs_ready, s, e->ev_reset, nullptr, [&](hipStream_t c) {
+        k_reset_batch<<<grid_for(m, RESET_BLOCK, RESET_GRID), RESET_BLOCK, 0, c>>>(
+            (uint64_t)m, key, ts, cfg, status, e->d_cfg, (uint32_t)e->h_cfg.size(), e->d_tb, e->tb_cap - 1, e->d_win,
+            e->win_cap - 1, e->spill());
+    });
+}
+
+// enqueue the peek or the reset step of the routed path (include/rl_route.h):
+// k_peek_routed / k_reset_routed as a chain op, ordered like run_peek and
+// run_reset_batch.  The kernel always waits for s: the merge produced count,
+// order and the store clocks there (RL_OPT_PIPELINE promises the caller's
+// arrays, not the router's).  Its end is recorded into `done` when given, else
+// so waits for it.  No buffer set is taken, so m_max is not bounded by
+// max_batch; nothing is counted in rl_stats; the one flag it can raise is
+// EF_ROUTED_OVER.
+static int run_routed_op(rl_engine* e, bool reset, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
+                         hipEvent_t done) {
+    const uint32_t ncfg = (uint32_t)e->h_cfg.size();
+    return chain_op(e, s, false, so, reset ? e->ev_reset : e->ev_peek, done, [&](hipStream_t c) {
+        if (reset)
+            k_reset_routed<<<grid_for(m_max, RESET_BLOCK, RESET_GRID), RESET_BLOCK, 0, c>>>(
+                (uint64_t)m_max, io, e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1, e->spill());
+        else
+            k_peek_routed<<<grid_for(m_max, PEEK_BLOCK, PEEK_GRID), PEEK_BLOCK, 0, c>>>(
+                (uint64_t)m_max, io, e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1, e->spill(),
+                e->profile);
+    });
+}
+
+// the C-ABI of both routed steps: argument checks as rl_decide_routed_device_io
+// / _ev, except that m_max is bounded by the 32-bit `order` only
+static int routed_op_entry(rl_engine* e, bool reset, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                           const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
+                           void* out_stream, void* done_event) {
+    if (!e || !count || (m_max && (!recv || !order || !server_ms || !res))) return RL_EINVAL;
+    if (m_max > (size_t)UINT32_MAX) return fail(e, RL_EINVAL, "routed batch bound above the 32-bit order index");
+    (void)hipSetDevice(e->device);
+    hipStream_t s = in_stream ? (hipStream_t)in_stream : e->stream;
+    if (!m_max) {   // nothing to run: the event marks the caller's stream
+        if (done_event) HIPCHK(e, hipEventRecord((hipEvent_t)done_event, s));
+        return RL_OK;
+    }
+    const RoutedIo io{recv, order, count, server_ms, res, e->d_eflags};
+    return run_routed_op(e, reset, m_max, io, s, out_stream ? (hipStream_t)out_stream : s, (hipEvent_t)done_event);
+}
+
+extern "C" int rl_peek_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                                     const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
+                                     void* in_stream, void* out_stream, void* done_event) {
+    return routed_op_entry(e, false, m_max, count, recv, order, server_ms, res, in_stream, out_stream, done_event);
+}
+
+extern "C" int rl_reset_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                                      const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
+                                      void* in_stream, void* out_stream, void* done_event) {
+    return routed_op_entry(e, true, m_max, count, recv, order, server_ms, res, in_stream, out_stream, done_event);
+}
+
+// The routed peek and reset steps on an empty batch (they read the zero count
+// and nothing else), then k_peek and k_reset_batch on one request that is
+// rejected: no config is registered yet.  The staging arrays hold zeros.
+int rl::ops_warm_up(rl_engine* e) {
+    hipStream_t s = e->stream;
+    const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
+    for (const bool reset : {false, true}) {
+        const int r = run_routed_op(e, reset, 1, io, s, s, nullptr);
+        if (r != RL_OK) return r;
+    }
+    const ReqArgs a{e->d_key, e->d_ts, e->d_n, e->d_cfgid, nullptr, e->d_dec, e->d_rem, e->d_retry, e->d_reset, e->d_tok};
+    const int r = run_peek(e, 1, a, s, false);
+    if (r != RL_OK) return r;
+    return run_reset_batch(e, 1, e->d_key, e->d_ts, e->d_cfgid, e->d_dec, s, false);
+}
+
+int rl::ops_q14_slow(rl_engine* e, unsigned long long* out) {
+    HIPCHK(e, hipMemcpyFromSymbol(out, HIP_SYMBOL(rlq::q14_slow_calls), sizeof *out, 0, hipMemcpyDeviceToHost));
+    return RL_OK;
+}
+
+// The DEL only writes `when` fields of table entries: a chain op with its
+// arguments by value, so nothing to wait for.
+extern "C" int rl_reset_device(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns, void* stream) {
+    if (!e || cfg_id >= e->h_cfg.size() || key_id == EMPTY_KEY) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    return chain_op(e, s, true, s, e->ev_reset, nullptr, [&](hipStream_t c) {
+        k_reset<<<1, 1, 0, c>>>(key_id, ts_ns, e->d_cfg, cfg_id, e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1,
+                                e->spill());
+    });
+}
+
+extern "C" int rl_reset(rl_engine* e, uint32_t cfg_id, uint64_t key_id, int64_t ts_ns) {
+    const int r = rl_reset_device(e, cfg_id, key_id, ts_ns, nullptr);
+    if (r != RL_OK) return r;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return RL_OK;
+}
+
+// Many resets in one launch (rl_reset.h), ordered as rl_reset_device.  The
+// grid strides over any m: no chunking on the device entry point.
+extern "C" int rl_reset_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                     const uint32_t* cfg_id, uint8_t* status, void* stream) {
+    if (!e || (m && (!key_id || !ts_ns || !cfg_id))) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    return run_reset_batch(e, m, key_id, ts_ns, cfg_id, status, s, (e->flags & RL_OPT_PIPELINE) != 0);
+}
+
+extern "C" int rl_reset_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                              const uint32_t* cfg_id, uint8_t* status) {
+    if (!e || (m && (!key_id || !ts_ns || !cfg_id))) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    // chunks of max_batch: the size of the host API's staging arrays
+    for (size_t off = 0; off < m; off += e->max_batch) {
+        const uint32_t c = (uint32_t)std::min<size_t>(e->max_batch, m - off);
+        int r = stage_in(e, off, c, key_id, ts_ns, nullptr, cfg_id, nullptr, s);
+        // the staged inputs arrive on s: the kernel always waits for them
+        if (r == RL_OK) r = run_reset_batch(e, c, e->d_key, e->d_ts, e->d_cfgid, status ? e->d_dec : nullptr, s, false);
+        if (r == RL_OK) r = stage_out(e, off, c, status, nullptr, nullptr, nullptr, nullptr, s);
+        if (r != RL_OK) return r;
+        HIPCHK(e, hipStreamSynchronize(s));
+    }
+    return RL_OK;
+}
+
+extern "C" int rl_reset_grid_cap(void) { return RESET_GRID * RESET_BLOCK; }
+
+// Read-only queries (rl_peek.h), ordered as rl_reset_device.  A peek raises no
+// error flag, so the sticky status of rl_engine_sync never comes from one.
+extern "C" int rl_peek_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                    const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                                    uint8_t* decision, int64_t* remaining, int64_t* retry_after_ns,
+                                    int64_t* reset_at_ns, double* tokens, void* stream) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !decision || !remaining || !retry_after_ns || !reset_at_ns)))
+        return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    // the grid strides over any m: no chunking
+    ReqArgs a{key_id, ts_ns, n, cfg_id, server_ms, decision, remaining, retry_after_ns, reset_at_ns, tokens};
+    return run_peek(e, m, a, s, (e->flags & RL_OPT_PIPELINE) != 0);
+}
+
+extern "C" int rl_peek_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                             const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* decision,
+                             int64_t* remaining, int64_t* retry_after_ns, int64_t* reset_at_ns, double* tokens) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !decision || !remaining || !retry_after_ns || !reset_at_ns)))
+        return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    // chunks of max_batch: the size of the host API's staging arrays
+    for (size_t off = 0; off < m; off += e->max_batch) {
+        const uint32_t c = (uint32_t)std::min<size_t>(e->max_batch, m - off);
+        int r = stage_in(e, off, c, key_id, ts_ns, n, cfg_id, server_ms, s);
+        ReqArgs a{e->d_key, e->d_ts, e->d_n, e->d_cfgid, server_ms ? e->d_sms : nullptr,
+                  e->d_dec, e->d_rem, e->d_retry, e->d_reset, tokens ? e->d_tok : nullptr};
+        // the staged inputs arrive on s: the kernel always waits for them
+        if (r == RL_OK) r = run_peek(e, c, a, s, false);
+        if (r == RL_OK) r = stage_out(e, off, c, decision, remaining, retry_after_ns, reset_at_ns, tokens, s);
+        if (r != RL_OK) return r;
+        HIPCHK(e, hipStreamSynchronize(s));
+    }
+    return RL_OK;
+}
+
+extern "C" int rl_peek_grid_cap(void) { return PEEK_GRID * PEEK_BLOCK; }

@@ -20,7 +20,7 @@
 // MAX_PROBES or the table mask (probe_find, spill_lookup).
 #pragma once
 
-#include "rl_replay.h"
+#include "rl_batch.h"
 #include "rl_routed.h"
 #include "rl_semantics.h"
 #include "rl_table.h"

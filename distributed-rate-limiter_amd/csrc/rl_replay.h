@@ -10,26 +10,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include "rl_batch.h"
 #include "rl_semantics.h"
 #include "rl_sort.h"
 #include "rl_table.h"
 #include "rl_window.h"
 
 namespace rl {
-
-struct ReqArgs {
-    const uint64_t* key;
-    const int64_t* ts;
-    const int64_t* n;
-    const uint32_t* cfg;
-    const int64_t* sms;   // nullable: server clock = floor(ts / 1e6) (also in sorted order)
-    uint8_t* dec;
-    int64_t* rem;
-    int64_t* retry;
-    int64_t* reset;
-    double* tok;          // nullable
-    const uint8_t* fresh = nullptr;   // sorted order, nullable: the request inserted its key (REC_FRESH)
-};
 
 // State-independent token-bucket quantities of each request (sorted order),
 // computed in the permute pass: the previous request of the same key is the

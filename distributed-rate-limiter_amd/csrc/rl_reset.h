@@ -35,6 +35,23 @@ constexpr int RESET_GRID = 1024;
 // per-request status of a reset batch (RL_RESET_DONE / RL_INVALID, rl_engine.h)
 constexpr uint8_t RESET_DONE = 1, RESET_INVALID = 3;
 
+// Reset of one valid request: DEL of the key(s) AllowN would touch at *ts
+// (tokenbucket.go:136-144, slidingwindow.go:125-139, fixedwindow.go:118-128).
+// *ts is read only where a window start is needed.
+__device__ inline void reset_one(uint64_t k, const int64_t* ts, const CfgDev& C, TbEntry* tb, uint64_t tb_mask,
+                                 WinEntry* win, uint64_t win_mask, const Spill& spill) {
+    if (C.alg == ALG_TOKEN_BUCKET) {
+        const uint32_t s = probe_find(tb, tb_mask, k);
+        if (s != NO_SLOT) tb[s].when = ABSENT;
+        return;
+    }
+    const uint32_t s = probe_find(win, win_mask, k);
+    if (s == NO_SLOT) return;
+    const int64_t ws = window_start(*ts, C);
+    wk_delete(&win[s], spill, ws);
+    if (C.alg == ALG_SLIDING_WINDOW) wk_delete(&win[s], spill, ws - C.ttl_c);
+}
+
 // A key a later batch's grouping is inserting right now (k_probe's CAS,
 // RL_OPT_PIPELINE) reads either as an empty slot or as a key whose entry holds
 // the initial, absent state: nothing to delete in both cases, which is the key
@@ -62,7 +79,7 @@ __device__ __forceinline__ void reset_requests(uint64_t m, const uint64_t* __res
     for (uint64_t i = blockIdx.x * (uint64_t)RESET_BLOCK + threadIdx.x; i < m; i += (uint64_t)gridDim.x * RESET_BLOCK) {
         uint64_t k;
         uint32_t c, at = 0;
-        int64_t t = 0;   // the arrays' ts[i] is read below, only where a window start is needed
+        int64_t t = 0;   // the arrays' ts[i] is read by reset_one, only where a window start is needed
         if (RT) {
             int64_t sms;   // not used: a DEL does not look at the clock
             const rl_route_rec q = routed_request(io, f, i, at, sms);
@@ -77,17 +94,7 @@ __device__ __forceinline__ void reset_requests(uint64_t m, const uint64_t* __res
             continue;
         }
         const CfgDev C = cfgs[c];
-        if (C.alg == ALG_TOKEN_BUCKET) {
-            const uint32_t s = probe_find(tb, tb_mask, k);
-            if (s != NO_SLOT) tb[s].when = ABSENT;
-        } else {
-            const uint32_t s = probe_find(win, win_mask, k);
-            if (s != NO_SLOT) {
-                const int64_t ws = window_start(RT ? t : ts[i], C);
-                wk_delete(&win[s], spill, ws);
-                if (C.alg == ALG_SLIDING_WINDOW) wk_delete(&win[s], spill, ws - C.ttl_c);
-            }
-        }
+        reset_one(k, RT ? &t : &ts[i], C, tb, tb_mask, win, win_mask, spill);
         if (RT) routed_result(io, at, RESET_DONE, 0, 0, 0);
         else if (status) status[i] = RESET_DONE;
     }

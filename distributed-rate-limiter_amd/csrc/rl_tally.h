@@ -38,8 +38,9 @@
 // the tally's own memory only: it holds no pointer to a state table.
 //
 // The kernels are compiled in a translation unit of their own (rl_tally.hip,
-// which defines RL_TALLY_DEVICE): rl_engine.hip includes this header for the
-// types and the two launchers only and gains no device code.
+// which defines RL_TALLY_DEVICE, with the rl_tally_* entry points): the other
+// units include this header through rl_engine_impl.h for the types only and
+// gain no device code.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -70,14 +71,6 @@ struct TallyKey {      // rl_tally_key
 static_assert(sizeof(TallyKey) == 32, "TallyKey must be 32 bytes");
 
 typedef unsigned long long tally_u64;
-
-// rl_tally.hip: k_tally over m > 0 requests on stream s (probe bound
-// min(slots, TALLY_PROBES)); k_tally_clear: every record free, every counter 0
-hipError_t tally_launch(uint64_t m, const uint64_t* key, const uint32_t* cfg, const int64_t* n, const uint8_t* dec,
-                        uint32_t ncfg, tally_u64* cfgc, tally_u64* glob, TallyKey* keys, uint64_t slots,
-                        hipStream_t s);
-hipError_t tally_clear_launch(TallyKey* keys, uint64_t slots, tally_u64* cfgc, uint64_t cfg_words, tally_u64* glob,
-                              hipStream_t s);
 
 #ifdef RL_TALLY_DEVICE
 

@@ -420,16 +420,7 @@ __device__ inline void mode_scale(int32_t mode, int32_t E, double& P, double& R)
     }
 }
 
-// Committed runs of the chain, indexed by the run's first sorted position
-// (k_tb_expand's input; len is reset to 0 once the run is expanded)
-struct TbRuns {
-    uint16_t* len;       // requests in the run starting here (0: none), <= CH_TILE
-    int16_t* E;          // decade / binade exponent (XDEC: the floor + XRUN)
-    int64_t* D0;         // exact stored state before the run
-    int64_t* D1;         // exact stored state after it, as the chain resolved it
-    uint32_t* xlist;     // start positions of the runs of multi-decade windows (k_tb_expand_x)
-    uint32_t* xcnt;      // their count (a zeroed control word of the batch set)
-};
+// (TbRuns, the committed runs of the chain: rl_batch.h)
 
 struct RingSrc {
     const ChainShared& sh;

@@ -273,6 +273,51 @@ def test_one_id_two_tables(rl):
     r.close()
 
 
+def test_single_resets_against_batch(rl):
+    """the same resets through rl_reset one by one on one engine and through
+    one rl_reset_batch on another (both run the one device routine, reset_one):
+    the same keys afterwards, the same decisions from a following batch.  A
+    token-bucket key, fixed-window keys in a slot and in the spill, sliding-
+    window keys whose current or previous window is spilled."""
+    configs = [(1, 20, 12 * NS), (3, 100, 60 * NS), (2, 100, 60 * NS)]
+    a, b = Rig(rl, 0, configs), Rig(rl, 0, configs)
+    w = [(T0 // (60 * NS) + 1 + j) * 60 * NS for j in range(4)]
+    s0 = w[0] // 1_000_000
+    keys = np.arange(1, 25, dtype=np.uint64)
+    cfg = (keys % np.uint64(3)).astype(np.uint32)
+    for j in range(3):        # windows w0, w1, w2 all alive: w0 is in the spill
+        part = (keys, np.full(24, w[j] + 5 * NS), np.full(24, 7 + j), cfg, np.full(24, s0))
+        a.decide(part)
+        b.decide(part)
+    loc = locations(a.eng)
+    assert loc == locations(b.eng)
+    assert all(loc[(int(k), w[0] // NS)] == "spill" for k in keys[cfg != 0])
+    #        TB   absent TB  FW slot  FW spill  SW w1+w0(spill)  SW w2+w1  SW w3: w2 only
+    rkey = [3,    999,       4,       7,        5,               8,        11]
+    rcfg = [0,    0,         1,       1,        2,               2,        2]
+    rts = [T0,    T0,        w[2],    w[0] + NS, w[1] + 30 * NS, w[2] + NS, w[3] + NS]
+    before = engine_keys(rl, a.eng, s0)
+    for k, t, c in zip(rkey, rts, rcfg):
+        a.eng.reset(c, k, t)
+    assert (b.eng.reset_batch(rkey, rts, rcfg) == RESET_DONE).all()
+    assert a.eng.sync() == 0 and b.eng.sync() == 0
+    after = engine_keys(rl, a.eng, s0)
+    assert after == engine_keys(rl, b.eng, s0)
+    assert before - after == {(3, 0, 0), (4, 1, w[2] // NS), (7, 1, w[0] // NS), (5, 1, w[1] // NS),
+                              (5, 1, w[0] // NS), (8, 1, w[2] // NS), (8, 1, w[1] // NS), (11, 1, w[2] // NS)}
+    assert locations(a.eng) == locations(b.eng)
+    apply_resets(a.sim, rkey, rts, rcfg, len(configs), s0)
+    for j in (2, 1, 0, 3):    # every key at every window again: engine against engine, and against the oracle
+        part = (keys, np.full(24, w[j] + 6 * NS), np.full(24, 95), cfg, np.full(24, s0))
+        ra, rb = a.eng.decide(*part), b.eng.decide(*part)
+        for f in ("decision", "remaining", "retry_after_ns", "reset_at_ns"):
+            assert np.array_equal(getattr(ra, f), getattr(rb, f)), f"w{j} {f}"
+        assert np.array_equal(ra.tokens.view(np.uint64)[cfg == 0], rb.tokens.view(np.uint64)[cfg == 0]), f"w{j}"
+        assert_same(ra, a.sim.decide(*part), configs, cfg, f"w{j}")
+    a.close()
+    b.close()
+
+
 # --- duplicates -------------------------------------------------------------------
 
 @pytest.mark.parametrize("profile", [0, 1])
