@@ -15,9 +15,9 @@
 //
 // This unit is the decision path and the engine's life cycle only.  Peek and
 // Reset are rl_ops.hip, table maintenance and snapshots rl_tables.hip, the
-// usage tally rl_tally.hip, each a code object of its own, so that of the
-// decision kernels changes with none of them; rl_engine_impl.h is what they
-// share.
+// usage tally rl_tally.hip, the top keys rl_hot.hip, each a code object of its
+// own, so that of the decision kernels changes with none of them;
+// rl_engine_impl.h is what they share.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -563,7 +563,8 @@ static void free_all(rl_engine* e) {
     (void)hipFree(e->d_key); (void)hipFree(e->d_ts); (void)hipFree(e->d_n); (void)hipFree(e->d_sms); (void)hipFree(e->d_cfgid);
     (void)hipFree(e->d_dec); (void)hipFree(e->d_rem); (void)hipFree(e->d_retry); (void)hipFree(e->d_reset); (void)hipFree(e->d_tok);
     (void)hipFree(e->d_tally_keys); (void)hipFree(e->d_tally_cfg); (void)hipFree(e->d_tally_glob);
-    for (auto& se : e->tally_ev) (void)hipEventDestroy(se.second);
+    (void)hipFree(e->d_hot_sketch); (void)hipFree(e->d_hot_keys); (void)hipFree(e->d_hot_glob);
+    for (auto& se : e->side_ev) (void)hipEventDestroy(se.second);
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     if (e->ev_small) (void)hipEventDestroy(e->ev_small);
@@ -584,10 +585,10 @@ int rl::drain(rl_engine* e) {
     for (auto& B : e->set)
         if (B.used) HIPCHK(e, hipEventSynchronize(B.back_done));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    // queued tallies read the accumulators (freed by destroy, moved when a
-    // config is registered) on streams of the caller's
-    for (auto& se : e->tally_ev) HIPCHK(e, hipEventSynchronize(se.second));
-    return RL_OK;
+    // queued tally and top-keys calls read their accumulators (freed by
+    // destroy, the tally's moved when a config is registered) on streams of
+    // the caller's
+    return side_wait(e);
 }
 
 static int warm_up(rl_engine* e);

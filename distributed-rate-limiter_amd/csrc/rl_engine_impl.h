@@ -1,8 +1,9 @@
 // rl_engine_impl.h -- the engine's host state and the helpers that more than
 // one translation unit of the library uses.  rl_engine.hip is the decision
 // path and the engine's life cycle; rl_ops.hip Peek and Reset; rl_tables.hip
-// table maintenance and snapshots; rl_tally.hip the usage tally.  Only
-// rl_engine.hip includes the replay (rl_replay.h): nothing here does.
+// table maintenance and snapshots; rl_tally.hip the usage tally; rl_hot.hip
+// the top keys.  Only rl_engine.hip includes the replay (rl_replay.h): nothing
+// here does.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 
 #include "../../include/rl_engine.h"
 #include "rl_batch.h"
+#include "rl_hot.h"
 #include "rl_semantics.h"
 #include "rl_table.h"
 #include "rl_tally.h"
@@ -178,9 +180,23 @@ struct rl_engine {
     uint32_t tally_cfg_cap = 0;
     rl::tally_u64* d_tally_glob = nullptr;    // TG_WORDS
     uint64_t tally_batches = 0, tally_requests = 0;
-    // the end of the last tally on each stream one was enqueued on: what
-    // drain() and rl_tally_read wait for (k_tally runs on the caller's stream)
-    std::vector<std::pair<hipStream_t, hipEvent_t>> tally_ev;
+
+    // top keys (rl_hot.h): off until rl_hot_enable
+    bool hot_on = false;
+    rl::hot_u64* d_hot_sketch = nullptr;      // HOT_DEPTH rows of hot_width counters
+    uint64_t hot_width = 0;
+    rl::HotKey* d_hot_keys = nullptr;         // hot_slots candidate records
+    uint64_t hot_slots = 0;
+    rl::hot_u64* d_hot_glob = nullptr;        // HG_WORDS
+    uint64_t hot_min = 0;
+    uint32_t hot_weight = 0;
+    uint64_t hot_batches = 0, hot_requests = 0;
+
+    // The tally's and the top keys' kernels run on the caller's stream and read
+    // the feature's own memory: the end of the last such call on each stream
+    // one was enqueued on is what drain(), rl_tally_read and rl_hot_read wait
+    // for (side_record / side_wait).
+    std::vector<std::pair<hipStream_t, hipEvent_t>> side_ev;
 };
 
 inline int fail(rl_engine* e, int code, const std::string& msg) {
@@ -206,6 +222,32 @@ int copy_out(T* dst, T src) {
     const uint32_t n = (uint32_t)std::min<size_t>(dst->struct_size, sizeof(T));
     src.struct_size = n;
     memcpy(dst, &src, n);
+    return RL_OK;
+}
+
+// record the end of a tally / top-keys call just enqueued on s
+inline int side_record(rl_engine* e, hipStream_t s) {
+    hipEvent_t ev = nullptr;
+    for (auto& se : e->side_ev)
+        if (se.first == s) ev = se.second;
+    if (!ev) {
+        if (e->side_ev.size() >= 16) {   // streams come and go: keep the list short
+            for (auto& se : e->side_ev) {
+                HIPCHK(e, hipEventSynchronize(se.second));
+                (void)hipEventDestroy(se.second);
+            }
+            e->side_ev.clear();
+        }
+        HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        e->side_ev.emplace_back(s, ev);
+    }
+    HIPCHK(e, hipEventRecord(ev, s));
+    return RL_OK;
+}
+
+// every tally / top-keys call enqueued so far, on any stream, has finished
+inline int side_wait(rl_engine* e) {
+    for (auto& se : e->side_ev) HIPCHK(e, hipEventSynchronize(se.second));
     return RL_OK;
 }
 

@@ -30,27 +30,14 @@ static hipError_t tally_clear_launch(TallyKey* keys, uint64_t slots, tally_u64* 
 // k_tally runs on the caller's stream, behind the finish of the batch it
 // counts; it touches the tally's own memory only, so it needs no order against
 // the engine's streams.  What must wait for it -- a read, a clear, a new
-// config's row, destroy -- waits for the event recorded behind the last tally
-// of every stream one was enqueued on (drain()).
+// config's row, destroy -- waits for the event recorded behind the last call
+// of every stream one was enqueued on (side_record; drain()).
 static int run_tally(rl_engine* e, size_t m, const uint64_t* key, const uint32_t* cfg, const int64_t* n,
                      const uint8_t* dec, hipStream_t s) {
-    hipEvent_t ev = nullptr;
-    for (auto& se : e->tally_ev)
-        if (se.first == s) ev = se.second;
-    if (!ev) {
-        if (e->tally_ev.size() >= 16) {   // streams come and go: keep the list short
-            for (auto& se : e->tally_ev) {
-                HIPCHK(e, hipEventSynchronize(se.second));
-                (void)hipEventDestroy(se.second);
-            }
-            e->tally_ev.clear();
-        }
-        HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        e->tally_ev.emplace_back(s, ev);
-    }
     HIPCHK(e, tally_launch((uint64_t)m, key, cfg, n, dec, (uint32_t)e->h_cfg.size(), e->d_tally_cfg, e->d_tally_glob,
                            e->d_tally_keys, e->tally_slots, s));
-    HIPCHK(e, hipEventRecord(ev, s));
+    const int r = side_record(e, s);
+    if (r != RL_OK) return r;
     e->tally_batches++;
     e->tally_requests += m;
     return RL_OK;
@@ -123,7 +110,10 @@ extern "C" int rl_tally_read(rl_engine* e, rl_tally_cfg* cfg_out, size_t cfg_cap
     static_assert(sizeof(rl_tally_cfg) == sizeof(tally_u64) * TALLY_CFG_WORDS, "rl_tally_cfg is a counter row");
     static_assert(sizeof(rl_tally_key) == sizeof(TallyKey), "rl_tally_key is a table record");
     (void)hipSetDevice(e->device);
-    for (auto& se : e->tally_ev) HIPCHK(e, hipEventSynchronize(se.second));
+    {
+        const int r = side_wait(e);
+        if (r != RL_OK) return r;
+    }
     hipStream_t s = e->stream;
     const uint32_t nc = (uint32_t)e->h_cfg.size();
     tally_u64 glob[TG_WORDS];

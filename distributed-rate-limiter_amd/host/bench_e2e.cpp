@@ -107,6 +107,7 @@ struct Args {
     int64_t linger_ns = 0;
     int64_t limit = 20;          // Token Bucket 100/min burst 20 = {Limit 20, Window 12 s}
     double window_s = 12.0;
+    uint64_t hot_min = 0;        // != 0: the top keys behind every batch (rl_coalescer_opts.hot_min)
 };
 
 }  // namespace
@@ -133,6 +134,7 @@ int main(int argc, char** argv) {
         else if (k == "--linger-us") a.linger_ns = (int64_t)(atof(v.c_str()) * 1000);
         else if (k == "--limit") a.limit = atol(v.c_str());
         else if (k == "--window-s") a.window_s = atof(v.c_str());
+        else if (k == "--hot-min") a.hot_min = strtoull(v.c_str(), nullptr, 10);
         else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     }
 
@@ -168,6 +170,7 @@ int main(int argc, char** argv) {
     co.max_in_flight = 3;
     co.linger_ns = a.linger_ns;
     co.queue_cap = 1ull << 26;
+    co.hot_min = a.hot_min;
     rl_coalescer* c = nullptr;
     if (rl_coalescer_create(e, &co, &c) != RL_OK) { fprintf(stderr, "coalescer create failed\n"); return 1; }
 

@@ -38,6 +38,7 @@ void Sub::carve(size_t m_) {
     info = rl_table_info{};
     snap = SnapArgs{};
     tally = TallyArgs{};
+    hot = HotArgs{};
     // layout by capacity, so a reused buffer keeps its arrays in place
     const size_t c = cap;
     uint8_t* p = mem.get();
@@ -109,8 +110,8 @@ public:
         M_ = M;
         return RL_OK;
     }
-    int launch(int i, Slot& s) override { return launch_on(i, s, rl_decide_batch_device, tally_); }
-    int launch_peek(int i, Slot& s) override { return launch_on(i, s, rl_peek_batch_device, false); }
+    int launch(int i, Slot& s) override { return launch_on(i, s, rl_decide_batch_device, tally_, hot_); }
+    int launch_peek(int i, Slot& s) override { return launch_on(i, s, rl_peek_batch_device, false, false); }
     int tally_enable(uint32_t key_slots) override {
         (void)hipSetDevice(dev_id_);
         rl_tally_opts o{sizeof(rl_tally_opts), key_slots};
@@ -126,13 +127,24 @@ public:
         (void)hipSetDevice(dev_id_);
         return rl_tally_read(e_, a.cfg_out, a.cfg_cap, a.ncfg, a.key_out, a.key_cap, a.keys_tracked, a.info, a.clear);
     }
+    int hot_enable(const rl_hot_opts& o) override {
+        (void)hipSetDevice(dev_id_);
+        const int rc = rl_hot_enable(e_, &o);
+        hot_ = rc == RL_OK;
+        return rc;
+    }
+    // as tally_read: rl_hot_read waits for the last call enqueued on os_
+    int hot_read(const HotArgs& a) override {
+        (void)hipSetDevice(dev_id_);
+        return rl_hot_read(e_, a.key_out, a.key_cap, a.keys_tracked, a.info, a.clear);
+    }
     // rl_decide_batch_device / rl_peek_batch_device: one argument list
     using DeviceFn = int (*)(rl_engine*, size_t, const uint64_t*, const int64_t*, const int64_t*, const uint32_t*,
                              const int64_t*, uint8_t*, int64_t*, int64_t*, int64_t*, double*, void*);
-    // tally: count the batch on os_ behind its results, on the arrays the
-    // decide used; the slot's completion event is recorded behind the tally,
-    // so the slot is not reused before it has run
-    int launch_on(int i, Slot& s, DeviceFn fn, bool tally) {
+    // tally, hot: count the batch on os_ behind its results, on the arrays the
+    // decide used (the tally first); the slot's completion event is recorded
+    // behind them, so the slot is not reused before they have run
+    int launch_on(int i, Slot& s, DeviceFn fn, bool tally, bool hot) {
         (void)hipSetDevice(dev_id_);   // the submitter thread
         Dev& d = dev_[i];
         Slot dv;
@@ -147,6 +159,7 @@ public:
             s.t_h2d = steady_ns();
             int rc = fn(e_, m, s.key, s.ts, s.n, s.cfg, nullptr, s.dec, s.rem, s.retry, s.reset, nullptr, os_);
             if (rc == RL_OK && tally) rc = rl_tally_batch_device(e_, m, s.key, s.cfg, s.n, s.dec, os_);
+            if (rc == RL_OK && hot) rc = rl_hot_batch_device(e_, m, s.key, s.cfg, s.n, s.dec, os_);
             if (rc != RL_OK) return rc;
             return hipEventRecord(d.ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
         }
@@ -160,6 +173,7 @@ public:
         s.t_h2d = steady_ns();
         int rc = fn(e_, m, dv.key, dv.ts, dv.n, dv.cfg, nullptr, dv.dec, dv.rem, dv.retry, dv.reset, nullptr, os_);
         if (rc == RL_OK && tally) rc = rl_tally_batch_device(e_, m, dv.key, dv.cfg, dv.n, dv.dec, os_);
+        if (rc == RL_OK && hot) rc = rl_hot_batch_device(e_, m, dv.key, dv.cfg, dv.n, dv.dec, os_);
         if (rc != RL_OK) return rc;
         ok = hipMemcpyAsync(s.dec, dv.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
         ok &= hipMemcpyAsync(s.rem, dv.rem, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
@@ -248,6 +262,7 @@ private:
     }
     rl_engine* e_;
     bool tally_ = false;         // tally_enable succeeded: launch() counts its batches
+    bool hot_ = false;           // hot_enable succeeded: the same for the top keys
     std::vector<int8_t> table_;  // table_of per config id (submitter thread)
     int dev_id_ = 0;             // the engine's device: current when the coalescer is created
     // batches up to this size run zero-copy on the pinned slot (larger ones:
@@ -355,6 +370,120 @@ private:
     rl_tally_info info_{};
 };
 
+// The top keys over a host backend: the sketch and candidate table of
+// csrc/rl_hot.h in plain C++ -- per backend batch every counted request's adds
+// (A), then the look at the batch's keys (B): estimate = the minimum of the
+// key's four counters; at or above hot_min the key is looked up in the table
+// (home slot mix64(key) & mask, linear probing over min(slots, 64) slots, never
+// released before a clear) and inserted when absent.  A config id counts as
+// known by HostTally's rule: from the first request of it the backend decided
+// (any decision but RL_INVALID), up to HostTally::MAX_ROWS ids.
+class HostHot {
+public:
+    static constexpr uint64_t PROBES = 64;
+    int enable(const rl_hot_opts& o) {
+        if (o.struct_size != sizeof(rl_hot_opts) || o.width > (1u << 24) || o.key_slots > (1u << 24) ||
+            o.weight > RL_HOT_UNITS || o.hot_min < 1)
+            return RL_EINVAL;
+        uint64_t width = 16, slots = 16;
+        while (width < (o.width ? o.width : 1u << 18)) width *= 2;
+        while (slots < (o.key_slots ? o.key_slots : 65536u)) slots *= 2;
+        width_ = width;
+        units_ = o.weight == RL_HOT_UNITS;
+        hot_min_ = o.hot_min;
+        sketch_.assign(RL_HOT_DEPTH * width, 0);
+        keys_.assign(slots, free_key());
+        for (int r = 0; r < RL_HOT_DEPTH; r++) salt_[r] = mix64((uint64_t)r + 1);
+        return RL_OK;
+    }
+    void add(size_t m, const uint64_t* key, const uint32_t* cfg, const int64_t* n, const uint8_t* dec) {
+        info_.batches++;
+        info_.requests += m;
+        counted_.assign(m, 0);
+        for (size_t i = 0; i < m; i++) {                         // (A)
+            const uint32_t c = cfg[i], d = dec[i];
+            if (c >= ncfg_) {
+                if (d >= RL_INVALID || c >= HostTally::MAX_ROWS) { info_.skipped++; continue; }
+                ncfg_ = c + 1;
+            }
+            if (d > RL_ERROR || key[i] == RL_KEY_RESERVED || (units_ && n[i] <= 0)) { info_.skipped++; continue; }
+            const uint64_t w = units_ ? (uint64_t)n[i] : 1;
+            counted_[i] = 1;
+            info_.total += w;
+            for (int r = 0; r < RL_HOT_DEPTH; r++) sketch_[r * width_ + col(key[i], r)] += w;
+        }
+        for (size_t i = 0; i < m; i++)                            // (B)
+            if (counted_[i] && estimate(key[i]) >= hot_min_) claim(key[i], cfg[i]);
+    }
+    int read(const HotArgs& a) {
+        if (a.key_out && a.key_cap) {
+            std::vector<rl_hot_key> tab;
+            for (const auto& r : keys_)
+                if (r.key_id != RL_KEY_RESERVED) tab.push_back(rl_hot_key{r.key_id, estimate(r.key_id), r.cfg_id, 0});
+            const size_t want = std::min(a.key_cap, tab.size());
+            std::partial_sort(tab.begin(), tab.begin() + want, tab.end(), [](const rl_hot_key& x, const rl_hot_key& y) {
+                return x.estimate != y.estimate ? x.estimate > y.estimate : x.key_id < y.key_id;
+            });
+            memcpy(a.key_out, tab.data(), sizeof(rl_hot_key) * want);
+        }
+        if (a.keys_tracked) *a.keys_tracked = info_.keys_tracked;
+        if (a.info) {
+            if (a.info->struct_size < 8) return RL_EINVAL;
+            rl_hot_info I = info_;
+            I.width = width_;
+            I.depth = RL_HOT_DEPTH;
+            I.key_slots = keys_.size();
+            I.hot_min = hot_min_;
+            I.weight = units_ ? RL_HOT_UNITS : RL_HOT_REQUESTS;
+            I.struct_size = (uint32_t)std::min<size_t>(a.info->struct_size, sizeof I);   // bytes filled in
+            memcpy(a.info, &I, I.struct_size);
+        }
+        if (a.clear) {
+            // the config ids seen stay known
+            std::fill(sketch_.begin(), sketch_.end(), 0);
+            std::fill(keys_.begin(), keys_.end(), free_key());
+            info_ = rl_hot_info{};
+        }
+        return RL_OK;
+    }
+
+private:
+    static rl_hot_key free_key() { return rl_hot_key{RL_KEY_RESERVED, 0, 0, 0}; }
+    static uint64_t mix64(uint64_t x) {   // csrc/rl_table.h
+        x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL;
+        x ^= x >> 27; x *= 0x94d049bb133111ebULL;
+        x ^= x >> 31; return x;
+    }
+    uint64_t col(uint64_t k, int r) const { return mix64(k ^ salt_[r]) & (width_ - 1); }
+    uint64_t estimate(uint64_t k) const {
+        uint64_t est = ~0ull;
+        for (int r = 0; r < RL_HOT_DEPTH; r++) est = std::min(est, sketch_[r * width_ + col(k, r)]);
+        return est;
+    }
+    void claim(uint64_t k, uint32_t c) {
+        const uint64_t mask = keys_.size() - 1, probes = std::min<uint64_t>(keys_.size(), PROBES);
+        uint64_t s = mix64(k) & mask;
+        for (uint64_t p = 0; p < probes; p++, s = (s + 1) & mask) {
+            rl_hot_key& r = keys_[s];
+            if (r.key_id == RL_KEY_RESERVED) {
+                r.key_id = k;
+                r.cfg_id = c;
+                info_.keys_tracked++;
+            }
+            if (r.key_id == k) return;
+        }
+        info_.dropped = 1;
+    }
+    std::vector<uint64_t> sketch_;
+    std::vector<rl_hot_key> keys_;
+    std::vector<uint8_t> counted_;
+    uint64_t salt_[RL_HOT_DEPTH] = {};
+    uint64_t width_ = 0, hot_min_ = 0;
+    uint32_t ncfg_ = 0;
+    bool units_ = false;
+    rl_hot_info info_{};
+};
+
 // synchronous host functions (the CPU tests plug the oracle in here)
 class FnBackend : public Backend {
 public:
@@ -365,6 +494,12 @@ public:
         return rc;
     }
     int tally_read(const TallyArgs& a) override { return tally_on_ ? tally_.read(a) : RL_EINVAL; }
+    int hot_enable(const rl_hot_opts& o) override {
+        const int rc = hot_.enable(o);
+        hot_on_ = rc == RL_OK;
+        return rc;
+    }
+    int hot_read(const HotArgs& a) override { return hot_on_ ? hot_.read(a) : RL_EINVAL; }
     int init(int nslots, size_t M, std::vector<Slot>* slots) override {
         slots->resize(nslots);
         mem_.resize(nslots);
@@ -388,6 +523,7 @@ public:
         const int rc = b_.batch(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset);
         // launch() and tally_read() both run on the submitter thread
         if (rc == RL_OK && tally_on_) tally_.add(s.m, s.key, s.cfg, s.n, s.dec);
+        if (rc == RL_OK && hot_on_) hot_.add(s.m, s.key, s.cfg, s.n, s.dec);
         return rc;
     }
     int launch_reset_batch(int, Slot& s) override {
@@ -419,6 +555,8 @@ private:
     rl_coalescer_backend b_;
     HostTally tally_;
     bool tally_on_ = false;
+    HostHot hot_;
+    bool hot_on_ = false;
     std::vector<std::unique_ptr<uint8_t[]>> mem_;
 };
 
@@ -448,6 +586,11 @@ int Coalescer::start() {
     if (rc != RL_OK) return rc;
     if (o_.tally_key_slots) {
         rc = be_->tally_enable(o_.tally_key_slots);
+        if (rc != RL_OK) return rc;
+    }
+    if (o_.hot_min) {
+        rl_hot_opts h{sizeof(rl_hot_opts), o_.hot_width, o_.hot_key_slots, o_.hot_weight, o_.hot_min};
+        rc = be_->hot_enable(h);
         if (rc != RL_OK) return rc;
     }
     t_sub_ = std::thread([this] { submitter(); });
@@ -535,12 +678,14 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
 }
 
 int Coalescer::SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
-                        uint64_t cap_win, uint64_t* ticket, void* tag, const SnapArgs* snap, const TallyArgs* tally) {
+                        uint64_t cap_win, uint64_t* ticket, void* tag, const SnapArgs* snap, const TallyArgs* tally,
+                        const HotArgs* hot) {
     Sub* s = get_sub(1);
     s->op = op;
     s->tag = tag;
     if (snap) s->snap = *snap;
     if (tally) s->tally = *tally;
+    if (hot) s->hot = *hot;
     s->key[0] = key;
     s->ts[0] = ts;
     s->n[0] = 1;
@@ -734,6 +879,8 @@ int Coalescer::run_table_op(Sub* op) {
     } else if (op->op == OP_TALLY) {
         // every batch before it is launched, its tally enqueued behind it
         st = be_->tally_read(op->tally);
+    } else if (op->op == OP_HOT) {
+        st = be_->hot_read(op->hot);
     } else if (op->op == OP_SNAPSHOT) {
         st = be_->snapshot(op->now_ms, op->snap.world, op->snap.rank, op->snap.buf, op->snap.len, op->snap.out);
     } else {
@@ -875,8 +1022,8 @@ void Coalescer::submitter() {
             if (f->waiting) f->cv.notify_all();
             notify_locked(f);
             maybe_free_locked(f);
-            // a manual GC invalidates the automatic GC's count (a tally read touches no table)
-            if (fop != OP_TALLY) gc_counted_ = false;
+            // a manual GC invalidates the automatic GC's count (a tally or top-keys read touches no table)
+            if (fop != OP_TALLY && fop != OP_HOT) gc_counted_ = false;
             continue;
         }
         const int si = next_slot_;
@@ -1055,6 +1202,8 @@ static int create(std::unique_ptr<rlc::Backend> be, const rl_coalescer_opts* opt
             return RL_EINVAL;
         memcpy(&o, opts, opts->struct_size);
         o.struct_size = sizeof o;
+        // the top keys' options count only from a struct that holds all four
+        if (opts->struct_size < sizeof(rl_coalescer_opts)) o.hot_width = o.hot_key_slots = o.hot_weight = 0, o.hot_min = 0;
     }
     auto* c = new rlc::Coalescer(std::move(be), o);
     int rc = c->start();
@@ -1177,9 +1326,10 @@ extern "C" int rl_coalescer_peek(rl_coalescer* c, size_t m, const uint64_t* key_
 }
 
 static int table_op(rl_coalescer* c, rlc::Op op, int64_t now_ms, uint64_t tb, uint64_t win, rl_table_info* out,
-                    const rlc::SnapArgs* snap = nullptr, const rlc::TallyArgs* tally = nullptr) {
+                    const rlc::SnapArgs* snap = nullptr, const rlc::TallyArgs* tally = nullptr,
+                    const rlc::HotArgs* hot = nullptr) {
     uint64_t t;
-    int rc = c->c->SubmitOp(op, 0, 0, 0, now_ms, tb, win, &t, nullptr, snap, tally);
+    int rc = c->c->SubmitOp(op, 0, 0, 0, now_ms, tb, win, &t, nullptr, snap, tally, hot);
     if (rc != RL_OK) return rc;
     rl_table_info info{};
     rc = c->c->Wait(t, -1, nullptr, nullptr, nullptr, nullptr, nullptr, &info);
@@ -1237,6 +1387,18 @@ extern "C" int rl_coalescer_tally(rl_coalescer* c, rl_tally_cfg* cfg_out, size_t
     a.info = info;
     a.clear = clear;
     return table_op(c, rlc::OP_TALLY, 0, 0, 0, nullptr, nullptr, &a);
+}
+
+extern "C" int rl_coalescer_hot(rl_coalescer* c, rl_hot_key* key_out, size_t key_cap, uint64_t* keys_tracked,
+                                rl_hot_info* info, int clear) {
+    if (!c || !c->c->HotOn() || (info && info->struct_size < 8)) return RL_EINVAL;
+    rlc::HotArgs a;
+    a.key_out = key_out;
+    a.key_cap = key_cap;
+    a.keys_tracked = keys_tracked;
+    a.info = info;
+    a.clear = clear;
+    return table_op(c, rlc::OP_HOT, 0, 0, 0, nullptr, nullptr, nullptr, &a);
 }
 
 extern "C" int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out) {

@@ -60,6 +60,15 @@ struct TallyArgs {
     int clear = 0;
 };
 
+// OP_HOT arguments (rl_hot_read's), as TallyArgs
+struct HotArgs {
+    rl_hot_key* key_out = nullptr;
+    size_t key_cap = 0;
+    uint64_t* keys_tracked = nullptr;
+    rl_hot_info* info = nullptr;
+    int clear = 0;
+};
+
 // where batches go: the GPU engine, or synchronous host functions (tests)
 class Backend {
 public:
@@ -69,6 +78,11 @@ public:
     virtual int tally_enable(uint32_t key_slots) = 0;
     // rl_tally_read: every batch launched so far is counted (synchronous)
     virtual int tally_read(const TallyArgs& a) = 0;
+    // top keys (rl_coalescer_opts.hot_min): once enabled, launch() counts every
+    // batch behind its decisions (and behind its tally), as one rl_hot_batch call
+    virtual int hot_enable(const rl_hot_opts& o) = 0;
+    // rl_hot_read: every batch launched so far is counted (synchronous)
+    virtual int hot_read(const HotArgs& a) = 0;
     virtual int init(int nslots, size_t max_batch, std::vector<Slot>* slots) = 0;
     virtual int launch(int slot, Slot& s) = 0;   // asynchronous
     // the slot's s.m resets (key, ts, cfg; rl_reset_batch_device) after every
@@ -101,7 +115,7 @@ public:
 std::unique_ptr<Backend> make_gpu_backend(rl_engine* e);
 std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b);
 
-enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY };
+enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT };
 // submissions that carry requests and results (the rest carry one operation)
 inline bool has_requests(Op op) { return op == OP_REQ || op == OP_PEEK; }
 // submissions the submitter takes from the queue in parts of up to max_batch:
@@ -143,6 +157,7 @@ struct Sub {
     rl_table_info info{};
     SnapArgs snap;
     TallyArgs tally;              // OP_TALLY
+    HotArgs hot;                  // OP_HOT
     std::condition_variable cv;
     std::unique_ptr<uint8_t[]> mem;
     uint64_t* key;
@@ -183,9 +198,11 @@ public:
     // snapshot / restore, queued in sequence order
     int SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
                  uint64_t cap_win, uint64_t* ticket, void* tag = nullptr, const SnapArgs* snap = nullptr,
-                 const TallyArgs* tally = nullptr);
+                 const TallyArgs* tally = nullptr, const HotArgs* hot = nullptr);
     // rl_coalescer_opts.tally_key_slots != 0
     bool TallyOn() const { return o_.tally_key_slots != 0; }
+    // rl_coalescer_opts.hot_min != 0
+    bool HotOn() const { return o_.hot_min != 0; }
     // Completion callback for submissions made with a tag: fn(user, ticket,
     // tag) runs once when the submission is done (applied, failed, or dropped
     // unapplied), on a coalescer thread (or the thread of a Cancel / Wait that

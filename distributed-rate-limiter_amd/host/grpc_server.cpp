@@ -33,6 +33,7 @@
 #include <string_view>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/rl_keyhash.h"
@@ -224,8 +225,12 @@ struct Io;
 struct Conn;
 
 // K_PEEK: a read-only AllowN (rl_coalescer_peek); K_RESET_BATCH: many resets, one coalescer submission;
-// K_USAGE: RateLimiterMetrics.Usage, one rl_coalescer_tally
-enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE };
+// K_USAGE: RateLimiterMetrics.Usage, one rl_coalescer_tally; K_TOPKEYS: RateLimiterTopKeys.TopKeys, one
+// rl_coalescer_hot
+enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE, K_TOPKEYS };
+// a queued read that writes into buffers its Rpc owns: not cancelled when its
+// client goes away, but detached and left to finish
+inline bool is_read(Kind k) { return k == K_USAGE || k == K_TOPKEYS; }
 
 // what a Usage RPC's tally read writes into (OP_TALLY runs on the submitter
 // thread): owned by the Rpc, which stays in its loop's table until the read is
@@ -236,6 +241,13 @@ struct UsageBuf {
     uint32_t ncfg = 0;
     uint64_t tracked = 0;
     rl_tally_info info{};
+};
+
+// the same for a TopKeys RPC's read (OP_HOT)
+struct HotBuf {
+    std::vector<rl_hot_key> keys;
+    uint64_t tracked = 0;
+    rl_hot_info info{};
 };
 
 struct Stream {
@@ -252,7 +264,8 @@ struct BatchItem {
     int64_t n;
     int err;                   // 0: submitted; 1: unknown limiter; 2: invalid n
     std::string name;          // the unknown limiter's name
-    std::string key;           // with the tally on: the key's name (remembered if it is denied)
+    std::string key;           // Rpc.named: the key's name (remembered if it is denied or watched)
+    uint64_t id = 0;           // Rpc.named: its key id
 };
 
 struct Rpc {
@@ -264,8 +277,11 @@ struct Rpc {
     const Limiter* lim = nullptr;
     std::vector<BatchItem> items;
     size_t m = 0;              // requests submitted
-    std::string key;           // K_ALLOW with the tally on: the key's name
+    std::string key;           // K_ALLOW, named: the key's name
+    uint64_t id = 0;           // K_ALLOW, named: its key id
+    bool named = false;        // the names were kept (Server::keep_names when the RPC came in)
     std::unique_ptr<UsageBuf> usage;   // K_USAGE
+    std::unique_ptr<HotBuf> hot;       // K_TOPKEYS
 };
 
 struct Server;
@@ -290,6 +306,8 @@ struct Io {
     std::unordered_map<uint64_t, Rpc> rpcs; // by ticket
     std::vector<Conn*> conns;
     std::vector<Conn*> dirty;
+    // odd while this loop looks an id up in the watch set (Server::watched)
+    std::atomic<uint64_t> watch_seq{0};
     using Dl = std::pair<int64_t, uint64_t>;
     std::priority_queue<Dl, std::vector<Dl>, std::greater<Dl>> deadlines;
 };
@@ -315,9 +333,69 @@ struct Server {
     std::unordered_map<uint64_t, std::pair<std::string, uint64_t>> names;   // id -> (name, stamp)
     std::deque<std::pair<uint64_t, uint64_t>> names_order;                  // (id, stamp), oldest first
     uint64_t names_stamp = 0;
-    void remember(const Limiter* l, std::string_view key) {
-        if (!tally || !names_cap) return;
-        const uint64_t id = key_id(l, key);
+    // RateLimiterTopKeys.TopKeys: on when the coalescer keeps the top keys.
+    // The watch set is the key ids of the latest TopKeys response, names_cap
+    // at most: a request of one of them records its name in `names`, so a hot
+    // key that is never denied is named from the second scrape on.  The set is
+    // immutable and published through one pointer, null while it is empty: a
+    // request path that finds it null does nothing, one that finds a set
+    // looks its id up without a lock.  A replaced set is freed once no loop
+    // can still be reading it: a loop's watch_seq is odd while it reads, so a
+    // loop that was outside a read after the exchange, or has left the read it
+    // was in, only ever sees the new pointer.
+    using WatchSet = std::unordered_set<uint64_t>;
+    bool hot = false;
+    std::atomic<const WatchSet*> watch{nullptr};
+    struct Retired {
+        const WatchSet* set;
+        std::vector<uint64_t> seq;   // every loop's watch_seq after the exchange
+    };
+    std::mutex watch_mu;             // publishers only
+    std::vector<Retired> retired;
+    // names are kept for the requests of an RPC that comes in now
+    bool keep_names() const { return names_cap && (tally || watch.load(std::memory_order_relaxed) != nullptr); }
+    bool watched(Io* io, uint64_t id) {
+        if (!watch.load(std::memory_order_relaxed)) return false;
+        io->watch_seq.fetch_add(1);
+        const WatchSet* w = watch.load();
+        const bool hit = w && w->count(id) != 0;
+        io->watch_seq.fetch_add(1);
+        return hit;
+    }
+    void publish_watch(const rl_hot_key* keys, size_t n) {
+        WatchSet* w = nullptr;
+        n = std::min(n, names_cap);
+        if (n) {
+            w = new WatchSet();
+            w->reserve(n);
+            for (size_t i = 0; i < n; i++) w->insert(keys[i].key_id);
+        }
+        std::lock_guard<std::mutex> g(watch_mu);
+        const WatchSet* old = watch.exchange(w);
+        if (old) {
+            Retired r{old, {}};
+            for (auto& io : ios) r.seq.push_back(io->watch_seq.load());
+            retired.push_back(std::move(r));
+        }
+        for (size_t i = 0; i < retired.size();) {
+            bool quiet = true;
+            for (size_t j = 0; j < ios.size(); j++)
+                quiet = quiet && (!(retired[i].seq[j] & 1) || ios[j]->watch_seq.load() != retired[i].seq[j]);
+            if (quiet) {
+                delete retired[i].set;
+                retired[i] = std::move(retired.back());
+                retired.pop_back();
+            } else {
+                i++;
+            }
+        }
+    }
+    ~Server() {
+        delete watch.load();
+        for (auto& r : retired) delete r.set;
+    }
+    void remember(uint64_t id, std::string_view key) {
+        if (!names_cap) return;
         std::lock_guard<std::mutex> g(names_mu);
         const uint64_t stamp = ++names_stamp;
         names[id] = {std::string(key), stamp};
@@ -515,6 +593,35 @@ void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, c
         put_int(msg, 4, (int64_t)u.tracked);
         return respond_ok(c, st, msg);
     }
+    if (rpc.kind == K_TOPKEYS) {
+        Server* s = io->srv;
+        if (rc == RL_EINVAL) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "top keys are off");
+        if (rc != RL_OK) return respond_err(c, st, GRPC_UNAVAILABLE, "failed to read top keys: engine status " + std::to_string(rc));
+        const HotBuf& h = *rpc.hot;
+        const size_t nk = (size_t)std::min<uint64_t>(h.keys.size(), h.tracked);
+        std::string one;
+        for (size_t i = 0; i < nk; i++) {        // TopKeysResponse.keys = 1
+            const rl_hot_key& k = h.keys[i];
+            one.clear();
+            for (const Limiter& l : s->lims)
+                if (l.cfg == k.cfg_id) {
+                    put_bytes(one, 1, l.name);
+                    break;
+                }
+            put_fixed64(one, 2, k.key_id);
+            put_bytes(one, 3, s->name_of(k.key_id));
+            put_int(one, 4, (int64_t)k.estimate);
+            put_msg(msg, 1, one);
+        }
+        put_int(msg, 2, (int64_t)h.info.total);
+        put_int(msg, 3, (int64_t)h.tracked);
+        put_int(msg, 4, (int64_t)h.info.dropped);
+        put_int(msg, 5, (int64_t)h.info.width);
+        put_int(msg, 6, (int64_t)h.info.hot_min);
+        put_int(msg, 7, (int64_t)h.info.weight);
+        s->publish_watch(h.keys.data(), nk);     // this response's keys are watched from now on
+        return respond_ok(c, st, msg);
+    }
     if (rpc.kind == K_RESET_BATCH) {
         // ResetBatchResponse.errors = 1: one string per request, "" = done
         size_t j = 0;
@@ -538,7 +645,9 @@ void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, c
         else respond_ok(c, st, msg);
         return;
     }
-    if (rpc.kind == K_ALLOW && rc == RL_OK && dec && dec[0] == RL_DENIED) io->srv->remember(rpc.lim, rpc.key);
+    if (rpc.kind == K_ALLOW && rpc.named && rc == RL_OK && dec &&
+        ((dec[0] == RL_DENIED && io->srv->tally) || io->srv->watched(io, rpc.id)))
+        io->srv->remember(rpc.id, rpc.key);
     if (rpc.kind == K_ALLOW || rpc.kind == K_PEEK) {
         const Outcome o = decide_outcome(rpc.lim, rpc.t, rc, dec ? dec[0] : 0, rem ? rem[0] : 0, retry ? retry[0] : 0,
                                          reset ? reset[0] : 0);
@@ -553,7 +662,9 @@ void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, c
         if (b.err == 1) r.error = "unknown limiter " + py_repr(b.name);
         else if (b.err == 2) r.error = ERR_INVALID_N;
         else {
-            if (rc == RL_OK && dec && dec[j] == RL_DENIED) io->srv->remember(b.lim, b.key);
+            if (rpc.named && rc == RL_OK && dec &&
+                ((dec[j] == RL_DENIED && io->srv->tally) || io->srv->watched(io, b.id)))
+                io->srv->remember(b.id, b.key);
             r = decide_outcome(b.lim, rpc.t, rc, dec ? dec[j] : 0, rem ? rem[j] : 0, retry ? retry[j] : 0,
                                reset ? reset[j] : 0).r;
             j++;
@@ -695,6 +806,38 @@ void dispatch(Conn* c, Stream* st) {
         io->rpcs.emplace(ticket, std::move(rpc));
         return;
     }
+    if (p == "/ratelimiter.v1.RateLimiterTopKeys/TopKeys") {
+        if (!s->hot) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "top keys are off");
+        uint64_t top = 0, clear = 0;   // TopKeysRequest: top = 1, clear = 2
+        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
+        while (pb.more()) {
+            const uint64_t tag = pb.varint();
+            if ((tag >> 3) == 1 && (tag & 7) == 0) top = pb.varint() & 0xffffffffu;
+            else if ((tag >> 3) == 2 && (tag & 7) == 0) clear = pb.varint();
+            else pb.skip((uint32_t)(tag & 7));
+        }
+        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad TopKeysRequest");
+        // as Usage: one table operation in the coalescer's sequence, completed
+        // through the ticket's notification
+        Rpc rpc{c, st->id, K_TOPKEYS, 0, 0, nullptr, {}, 0};
+        rpc.hot.reset(new HotBuf());
+        HotBuf& h = *rpc.hot;
+        h.keys.assign((size_t)std::min<uint64_t>(top, 1u << 16), rl_hot_key{});
+        h.info.struct_size = sizeof h.info;
+        rlc::HotArgs a;
+        a.key_out = h.keys.data();
+        a.key_cap = h.keys.size();
+        a.keys_tracked = &h.tracked;
+        a.info = &h.info;
+        a.clear = clear != 0;
+        uint64_t ticket = 0;
+        const int rc = s->co->SubmitOp(rlc::OP_HOT, 0, 0, 0, 0, 0, 0, &ticket, io, nullptr, nullptr, &a);
+        if (rc != RL_OK) return finish_rpc(io, 0, rpc, rc, nullptr, nullptr, nullptr, nullptr);
+        st->pending = true;
+        st->ticket = ticket;
+        io->rpcs.emplace(ticket, std::move(rpc));
+        return;
+    }
     static const std::string peek_path = "/ratelimiter.v1.RateLimiterStatus/Peek";
     const bool is_peek = p == peek_path;
     if (!is_peek && p.compare(0, svc.size(), svc) != 0) return respond_err(c, st, GRPC_UNIMPLEMENTED, "unknown service");
@@ -713,13 +856,18 @@ void dispatch(Conn* c, Stream* st) {
         const uint64_t id = s->key_id(lim, r.key);
         const size_t mm = m == "Reset" ? 0 : 1;
         Rpc rpc{c, st->id, m == "Reset" ? K_RESET : is_peek ? K_PEEK : K_ALLOW, t, 0, lim, {}, mm};
-        if (s->tally && rpc.kind == K_ALLOW) rpc.key = std::string(r.key);
+        if (rpc.kind == K_ALLOW && s->keep_names()) {
+            rpc.named = true;
+            rpc.key = std::string(r.key);
+            rpc.id = id;
+        }
         const int64_t n = r.n;
         const uint32_t cfg = lim->cfg;
         return submit_rpc(io, c, st, std::move(rpc), mm, &id, &t, &n, &cfg);
     }
     if (m == "AllowBatch") {
         Rpc rpc{c, st->id, K_BATCH, s->now(), 0, nullptr, {}, 0};
+        rpc.named = s->keep_names();
         std::vector<uint64_t> key;
         std::vector<int64_t> ts, n;
         std::vector<uint32_t> cfg;
@@ -743,7 +891,10 @@ void dispatch(Conn* c, Stream* st) {
                 ts.push_back(rpc.t);
                 n.push_back(r.n);
                 cfg.push_back(it.lim->cfg);
-                if (s->tally) it.key = std::string(r.key);
+                if (rpc.named) {
+                    it.key = std::string(r.key);
+                    it.id = key.back();
+                }
             }
             rpc.items.push_back(std::move(it));
         }
@@ -817,7 +968,7 @@ int cb_close(nghttp2_session*, int32_t sid, uint32_t, void* u) {
         // and the buffers)
         Io* io = c->io;
         auto r = io->rpcs.find(st->ticket);
-        if (r != io->rpcs.end() && r->second.kind == K_USAGE) {
+        if (r != io->rpcs.end() && is_read(r->second.kind)) {
             r->second.conn = nullptr;
         } else {
             io->srv->co->Cancel(st->ticket);
@@ -841,7 +992,7 @@ void close_conn(Io* io, Conn* c) {
         Stream* st = kv.second.get();
         if (!st->pending) continue;
         auto r = io->rpcs.find(st->ticket);
-        if (r != io->rpcs.end() && r->second.kind == K_USAGE) {   // left to finish, detached: cb_close
+        if (r != io->rpcs.end() && is_read(r->second.kind)) {   // left to finish, detached: cb_close
             r->second.conn = nullptr;
             continue;
         }
@@ -1046,6 +1197,7 @@ extern "C" int rl_grpc_server_start(rl_coalescer* c, const rl_grpc_limiter* limi
     s.clock_start = o.clock_start_ns;
     s.clock_step = o.clock_step_ns;
     s.tally = o.tally != 0;
+    s.hot = co->HotOn();
     if (o.names_cap) s.names_cap = o.names_cap;
     s.lims.reserve(n_limiters);
     for (size_t i = 0; i < n_limiters; i++) {
@@ -1133,15 +1285,17 @@ extern "C" int rl_grpc_server_destroy(rl_grpc_server* g) {
     if (!g) return RL_EINVAL;
     rl_grpc_server_shutdown(g, 0);
     Server& s = g->s;
-    // a Usage read still queued or running when the loops ended writes into
+    // a Usage or TopKeys read still queued or running when the loops ended writes into
     // buffers its Rpc owns: wait for it (the loops have been joined), but not
     // for ever -- a coalescer that no longer runs its queue never completes
     // it -- and a read that has not ended by then keeps its buffers (leaked)
     for (auto& io : s.ios)
         for (auto& kv : io->rpcs)
-            if (kv.second.kind == K_USAGE &&
-                s.co->Wait(kv.first, 10LL * 1000000000LL, nullptr, nullptr, nullptr, nullptr) == RL_ETIMEOUT)
+            if (is_read(kv.second.kind) &&
+                s.co->Wait(kv.first, 10LL * 1000000000LL, nullptr, nullptr, nullptr, nullptr) == RL_ETIMEOUT) {
                 (void)kv.second.usage.release();
+                (void)kv.second.hot.release();
+            }
     s.co->SetNotify(nullptr, nullptr);
     for (auto& io : s.ios) {
         close(io->ep);

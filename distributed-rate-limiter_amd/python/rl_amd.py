@@ -109,6 +109,23 @@ TALLY_KEY = np.dtype([("key_id", np.uint64), ("denied", np.uint64), ("units_deni
                       ("cfg_id", np.uint32), ("pad_", np.uint32)])
 
 
+class rl_hot_opts(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("key_slots", C.c_uint32),
+                ("weight", C.c_uint32), ("hot_min", C.c_uint64)]
+
+
+class rl_hot_info(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("pad_", C.c_uint32)] + [
+        (k, C.c_uint64) for k in ("width", "depth", "key_slots", "hot_min", "weight", "keys_tracked", "dropped",
+                                  "total", "skipped", "batches", "requests")]
+
+
+# rl_hot_key as a numpy record
+HOT_KEY = np.dtype([("key_id", np.uint64), ("estimate", np.uint64), ("cfg_id", np.uint32), ("pad_", np.uint32)])
+HOT_REQUESTS, HOT_UNITS = 0, 1
+HOT_DEPTH = 4
+
+
 class rl_snapshot_info(_Sized):
     """include/rl_snapshot.h"""
     _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("profile", C.c_int32), ("world", C.c_uint32),
@@ -129,6 +146,19 @@ class rl_coalescer_opts(_Sized):
         ("gc_max_tb_capacity", C.c_uint64),
         ("gc_max_win_capacity", C.c_uint64),
         ("tally_key_slots", C.c_uint32),
+    ]
+
+
+class rl_coalescer_opts_hot(_Sized):
+    """rl_coalescer_opts with the top keys' trailing options: the whole struct
+    of include/rl_coalescer.h.  rl_coalescer_opts above is the struct up to
+    tally_key_slots, as a caller compiled before them passes it (its shorter
+    struct_size: top keys off)."""
+    _fields_ = rl_coalescer_opts._fields_ + [
+        ("hot_width", C.c_uint32),
+        ("hot_key_slots", C.c_uint32),
+        ("hot_weight", C.c_uint32),
+        ("hot_min", C.c_uint64),
     ]
 
 
@@ -175,6 +205,12 @@ _sig = {
     "rl_tally_grid_cap": (C.c_int, []),
     "rl_coalescer_tally": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), vp, C.c_size_t,
                                      C.POINTER(C.c_uint64), C.POINTER(rl_tally_info), C.c_int]),
+    "rl_hot_enable": (C.c_int, [vp, C.POINTER(rl_hot_opts)]),
+    "rl_hot_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
+    "rl_hot_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
+    "rl_hot_read": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(rl_hot_info), C.c_int]),
+    "rl_hot_grid_cap": (C.c_int, []),
+    "rl_coalescer_hot": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(rl_hot_info), C.c_int]),
     "rl_engine_sync": (C.c_int, [vp]),
     "rl_reset": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int64]),
     "rl_reset_device": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int64, vp]),
@@ -223,12 +259,11 @@ _sig = {
     "rll_add_logging": (C.c_int, [vp, C.c_size_t]),
     "rll_log_drain": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "rll_new_fail_closed_result": (C.c_int, [C.POINTER(rll_result)]),
-    "rl_coalescer_create": (C.c_int, [vp, C.POINTER(rl_coalescer_opts), C.POINTER(vp)]),
-    "rl_coalescer_create_with_backend": (C.c_int, [BATCH_FN, vp, C.POINTER(rl_coalescer_opts), C.POINTER(vp)]),
-    "rl_coalescer_create_with_backends": (C.c_int, [BATCH_FN, RESET_FN, vp, C.POINTER(rl_coalescer_opts),
-                                                    C.POINTER(vp)]),
-    "rl_coalescer_create_with_host_backend": (C.c_int, [C.POINTER(rl_coalescer_backend),
-                                                        C.POINTER(rl_coalescer_opts), C.POINTER(vp)]),
+    # the options by address: rl_coalescer_opts or rl_coalescer_opts_hot, told apart by struct_size
+    "rl_coalescer_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "rl_coalescer_create_with_backend": (C.c_int, [BATCH_FN, vp, vp, C.POINTER(vp)]),
+    "rl_coalescer_create_with_backends": (C.c_int, [BATCH_FN, RESET_FN, vp, vp, C.POINTER(vp)]),
+    "rl_coalescer_create_with_host_backend": (C.c_int, [C.POINTER(rl_coalescer_backend), vp, C.POINTER(vp)]),
     "rl_coalescer_reset": (C.c_int, [vp, C.c_uint64, C.c_int64, C.c_uint32]),
     "rl_coalescer_reset_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
     "rl_coalescer_now_ns": (C.c_int64, []),
@@ -304,6 +339,17 @@ PEEK_GRID_CAP = lib.rl_peek_grid_cap()
 RESET_GRID_CAP = lib.rl_reset_grid_cap()
 # the same of k_tally
 TALLY_GRID_CAP = lib.rl_tally_grid_cap()
+# the same of k_hot_add / k_hot_pick
+HOT_GRID_CAP = lib.rl_hot_grid_cap()
+
+
+@dataclass
+class Hot:
+    """rl_hot_read: keys the top candidates (HOT_KEY, largest estimate first),
+    info the rl_hot_info"""
+    keys: np.ndarray
+    keys_tracked: int
+    info: rl_hot_info
 
 
 @dataclass
@@ -526,6 +572,44 @@ class Engine:
         if rc != RL_OK:
             raise EngineError(rc, self.last_error())
         return Tally(cfg, keys[:min(top, tracked.value)], tracked.value, info)
+
+    def hot_enable(self, hot_min, width=0, key_slots=0, weight=HOT_REQUESTS):
+        """rl_hot_enable: allocate the top-keys sketch (width counters per row,
+        0 = 1 << 18) and candidate table (key_slots records, 0 = 65536); a key
+        whose estimate reaches hot_min becomes a candidate"""
+        o = rl_hot_opts(width=width, key_slots=key_slots, weight=weight, hot_min=hot_min)
+        rc = lib.rl_hot_enable(self.h, C.byref(o))
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def hot_batch(self, key, cfg, n, decision):
+        """rl_hot_batch: count one finished batch (host arrays, synchronous)"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        decision = np.ascontiguousarray(decision, dtype=np.uint8)
+        m = key.size
+        assert cfg.size == m and n.size == m and decision.size == m
+        rc = lib.rl_hot_batch(self.h, m, _ptr(key), _ptr(cfg), _ptr(n), _ptr(decision))
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def hot_batch_device(self, m, key_p, cfg_p, n_p, dec_p, stream=None):
+        """rl_hot_batch_device: the same with device pointers, enqueued on `stream`"""
+        rc = lib.rl_hot_batch_device(self.h, m, key_p, cfg_p, n_p, dec_p, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def hot_read(self, top=0, clear=False) -> Hot:
+        """rl_hot_read: the `top` candidates with the largest estimates, read
+        from the sketch as it is now; clear: zero everything afterwards"""
+        tracked, info = C.c_uint64(), rl_hot_info()
+        keys = np.zeros(top, HOT_KEY)
+        rc = lib.rl_hot_read(self.h, _ptr(keys) if top else None, top, C.byref(tracked), C.byref(info),
+                             1 if clear else 0)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        return Hot(keys[:min(top, tracked.value)], tracked.value, info)
 
     def stats(self) -> rl_stats:
         s = rl_stats()
@@ -947,12 +1031,16 @@ class Coalescer:
     `table_info`, `gc`, `peek`, `reset_batch`: the other backend functions,
     optional).
 
-    gc_interval_ns > 0 turns on the automatic table GC (rl_coalescer_opts)."""
+    gc_interval_ns > 0 turns on the automatic table GC (rl_coalescer_opts);
+    tally_key_slots the usage tally; hot_min (with hot_width, hot_key_slots,
+    hot_weight) the top keys."""
 
     def __init__(self, engine, max_batch=65536, max_in_flight=3, linger_ns=0, queue_cap=0, reset=None,
                  table_info=None, gc=None, peek=None, gc_interval_ns=0, gc_high_pct=0, gc_margin_ms=0,
-                 gc_max_tb_capacity=0, gc_max_win_capacity=0, reset_batch=None, tally_key_slots=0):
-        o = rl_coalescer_opts(max_batch=max_batch, max_in_flight=max_in_flight, gc_high_pct=gc_high_pct,
+                 gc_max_tb_capacity=0, gc_max_win_capacity=0, reset_batch=None, tally_key_slots=0, hot_min=0,
+                 hot_width=0, hot_key_slots=0, hot_weight=HOT_REQUESTS):
+        o = rl_coalescer_opts_hot(hot_min=hot_min, hot_width=hot_width, hot_key_slots=hot_key_slots, hot_weight=hot_weight,
+                              max_batch=max_batch, max_in_flight=max_in_flight, gc_high_pct=gc_high_pct,
                               linger_ns=linger_ns, queue_cap=queue_cap, gc_interval_ns=gc_interval_ns,
                               gc_margin_ms=gc_margin_ms, gc_max_tb_capacity=gc_max_tb_capacity,
                               gc_max_win_capacity=gc_max_win_capacity, tally_key_slots=tally_key_slots)
@@ -1064,6 +1152,18 @@ class Coalescer:
             return rc, None
         # rows of config ids >= max_configs are not returned (as rl_tally_read's cfg_cap)
         return rc, Tally(cfg[:min(ncfg.value, cfg.size)], keys[:min(top, tracked.value)], tracked.value, info)
+
+    def hot(self, top=0, clear=False):
+        """rl_coalescer_hot: the top keys in sequence order -- every request
+        submitted before the call is counted, none submitted after.
+        -> (rc, Hot); hot_min=0 at creation: RL_EINVAL"""
+        tracked, info = C.c_uint64(), rl_hot_info()
+        keys = np.zeros(top, HOT_KEY)
+        rc = lib.rl_coalescer_hot(self.h, _ptr(keys) if top else None, top, C.byref(tracked), C.byref(info),
+                                  1 if clear else 0)
+        if rc != RL_OK:
+            return rc, None
+        return rc, Hot(keys[:min(top, tracked.value)], tracked.value, info)
 
     def stats(self) -> rl_coalescer_stats:
         st = rl_coalescer_stats()

@@ -230,5 +230,16 @@ def usage(stub, top: int = 0, clear: bool = False, **kw):
     return stub.Usage(api("ratelimiter.proto").UsageRequest(top=top, clear=clear), **kw)
 
 
+def top_keys_stub(channel):
+    """the top-keys service (RateLimiterTopKeys: TopKeys)"""
+    return Stub(channel, api("ratelimiter.proto"), "RateLimiterTopKeys")
+
+
+def top_keys(stub, top: int = 0, clear: bool = False, **kw):
+    """RateLimiterTopKeys.TopKeys (stub: top_keys_stub(channel)) -> TopKeysResponse: the `top` keys with the largest
+    estimated weight over every decided request since the last clear, and the sketch's counters"""
+    return stub.TopKeys(api("ratelimiter.proto").TopKeysRequest(top=top, clear=clear), **kw)
+
+
 def health_stub(channel):
     return Stub(channel, api("health.proto"), "Health")

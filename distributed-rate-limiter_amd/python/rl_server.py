@@ -127,11 +127,18 @@ class RateLimiterService:
     with the backend; `clock()` -> Unix ns (time.Now())."""
 
     def __init__(self, limiters, coalescer, register, clock=time.time_ns, isolate=False, tally=False,
-                 names_cap=4096):
+                 names_cap=4096, hot=False):
         # tally: serve RateLimiterMetrics.Usage from the coalescer's usage
         # tally (created with tally_key_slots), and remember the names of the
         # last names_cap keys a denied response went out for (newest wins)
+        # hot: serve RateLimiterTopKeys.TopKeys from the coalescer's top keys
+        # (created with hot_min).  The watch set is the key ids of the latest
+        # TopKeys response, names_cap at most: a request of one of them records
+        # its name in the same map, so a hot key that is never denied is named
+        # from the second scrape on
         self.tally = tally
+        self.hot = hot
+        self.watch = frozenset()
         self.names_cap = names_cap
         self.names = {}                      # key id -> name, in insertion order
         self.names_lock = threading.Lock()
@@ -196,7 +203,7 @@ class RateLimiterService:
         t = self.clock()
         kid = self._key_id(lim, key)
         rc, (dec, rem, retry, reset) = self.co.decide(kid, t, n, lim.cfg_id, deadline_ns=self._deadline(ctx))
-        if rc == rl_amd.RL_OK and dec == rl_amd.DENIED:
+        if rc == rl_amd.RL_OK and ((dec == rl_amd.DENIED and self.tally) or kid in self.watch):
             self._remember(kid, key)
         res, err, code = self._result(lim, t, rc, dec, rem, retry, reset)
         if err:
@@ -204,8 +211,9 @@ class RateLimiterService:
         return res
 
     def _remember(self, kid: int, key: str):
-        """the name of a key a denied response goes out for (Usage reports it)"""
-        if not self.tally or self.names_cap <= 0:
+        """the name of a key a denied response goes out for (Usage reports
+        it), or of a key in the watch set (TopKeys does)"""
+        if not (self.tally or self.hot) or self.names_cap <= 0:
             return
         with self.names_lock:
             self.names.pop(kid, None)
@@ -241,6 +249,29 @@ class RateLimiterService:
             lim = by_cfg.get(int(r["cfg_id"]))
             out.keys.add(limiter=lim.name if lim else "", key_hash=int(r["key_id"]), key=names[int(r["key_id"])],
                          denied=int(r["denied"]), units_denied=int(r["units_denied"]))
+        return out
+
+    def TopKeys(self, req, ctx):
+        """one rl_coalescer_hot, in sequence order (blocks this handler thread,
+        not the server); its keys become the watch set"""
+        if not self.hot:
+            ctx.abort(grpc.StatusCode.FAILED_PRECONDITION, "top keys are off")
+        rc, h = self.co.hot(top=min(req.top, 1 << 16), clear=req.clear)
+        if rc == rl_amd.RL_EINVAL:
+            ctx.abort(grpc.StatusCode.FAILED_PRECONDITION, "top keys are off")
+        if rc != rl_amd.RL_OK:
+            ctx.abort(grpc.StatusCode.UNAVAILABLE, f"failed to read top keys: engine status {rc}")
+        by_cfg = {lim.cfg_id: lim for lim in reversed(list(self.by_name.values()))}
+        i = h.info
+        out = self.a.TopKeysResponse(total=i.total, keys_tracked=h.keys_tracked, dropped=i.dropped, width=i.width,
+                                     hot_min=i.hot_min, weight=i.weight)
+        ids = [int(r["key_id"]) for r in h.keys]
+        with self.names_lock:
+            names = {k: self.names.get(k, "") for k in ids}
+        for r, k in zip(h.keys, ids):
+            lim = by_cfg.get(int(r["cfg_id"]))
+            out.keys.add(limiter=lim.name if lim else "", key_hash=k, key=names[k], estimate=int(r["estimate"]))
+        self.watch = frozenset(ids[:max(self.names_cap, 0)])
         return out
 
     def Allow(self, req, ctx):
@@ -329,7 +360,7 @@ class RateLimiterService:
             rc, (dec, rem, retry, reset) = self.co.wait(tk, len(idx))
             for j, i in enumerate(idx):
                 lim = self.by_name[rs[i].limiter]
-                if rc == rl_amd.RL_OK and dec[j] == rl_amd.DENIED:
+                if rc == rl_amd.RL_OK and ((dec[j] == rl_amd.DENIED and self.tally) or int(kid[j]) in self.watch):
                     self._remember(int(kid[j]), rs[i].key)
                 res, err, _ = self._result(lim, t, rc, int(dec[j]), int(rem[j]), int(retry[j]), int(reset[j]))
                 out[i] = res if res is not None else self.a.AllowResponse(error=err)
@@ -347,6 +378,7 @@ def build_server(service: RateLimiterService, address: str, workers: int = 64) -
                          options=[("grpc.so_reuseport", 0)])
     for a, sname, impl in ((service.a, "RateLimiter", service), (service.a, "RateLimiterStatus", service),
                            (service.a, "RateLimiterAdmin", service), (service.a, "RateLimiterMetrics", service),
+                           (service.a, "RateLimiterTopKeys", service),
                            (service.h, "Health", service)):
         handlers = {}
         for mname, inp, out in a.services[sname]:
@@ -367,11 +399,13 @@ class GpuBackend:
         self.register = self.eng.register
         self.co = None
 
-    def start(self, max_batch=1 << 16, gc_interval_ns=NS, gc_margin_ms=1000, tally_key_slots=0):
+    def start(self, max_batch=1 << 16, gc_interval_ns=NS, gc_margin_ms=1000, tally_key_slots=0, **hot):
         """the coalescer, with the tables collected from the serving path
-        (tally_key_slots != 0: with the usage tally, RateLimiterMetrics.Usage)"""
+        (tally_key_slots != 0: with the usage tally, RateLimiterMetrics.Usage;
+        hot_min != 0, with hot_width, hot_key_slots and hot_weight: with the
+        top keys, RateLimiterTopKeys.TopKeys)"""
         self.co = rl_amd.Coalescer(self.eng, max_batch=max_batch, max_in_flight=3, gc_interval_ns=gc_interval_ns,
-                                   gc_margin_ms=gc_margin_ms, tally_key_slots=tally_key_slots)
+                                   gc_margin_ms=gc_margin_ms, tally_key_slots=tally_key_slots, **hot)
         return self.co
 
     def close(self):
@@ -447,10 +481,18 @@ def main(argv=None):
                          "the same prefix, as Redis keys are the formatted strings)")
     ap.add_argument("--tally-key-slots", type=int, default=0,
                     help="usage tally (RateLimiterMetrics.Usage): records of the throttled-key table, 0 = off")
+    ap.add_argument("--hot-min", type=int, default=0,
+                    help="top keys (RateLimiterTopKeys.TopKeys): a key whose estimated weight reaches this becomes "
+                         "a candidate, 0 = off")
+    ap.add_argument("--hot-width", type=int, default=0, help="top keys: counters per sketch row, 0 = 262144")
+    ap.add_argument("--hot-key-slots", type=int, default=0, help="top keys: candidate records, 0 = 65536")
+    ap.add_argument("--hot-units", action="store_true", help="top keys: weigh a request by n, not by 1")
     args = ap.parse_args(argv)
     specs = args.limiter or ["default:token_bucket:20:12s"]
     limiters = [Limiter.parse(s) for s in specs]
     be = GpuBackend(args.device, args.tb_capacity, args.win_capacity, args.max_batch)
+    hot = dict(hot_min=args.hot_min, hot_width=args.hot_width, hot_key_slots=args.hot_key_slots,
+               hot_weight=rl_amd.HOT_UNITS if args.hot_units else rl_amd.HOT_REQUESTS)
     print(f"rate limiter gRPC server on {args.address} ({args.frontend} front end): " + ", ".join(specs),
           file=sys.stderr, flush=True)
     try:
@@ -458,14 +500,14 @@ def main(argv=None):
             for lim in limiters:
                 lim.cfg_id = be.register(lim.alg, lim.limit, lim.window_ns)
             co = be.start(args.max_batch, int(args.gc_interval_ms * 1e6),
-                          args.gc_margin_ms, args.tally_key_slots)
+                          args.gc_margin_ms, args.tally_key_slots, **hot)
             serve_native(co, limiters, args.address, args.io_threads, args.isolate_limiters,
                          ready=lambda p: print(f"READY {p}", flush=True), tally=args.tally_key_slots != 0)
         else:
             svc = RateLimiterService(limiters, None, be.register, isolate=args.isolate_limiters,
-                                     tally=args.tally_key_slots != 0)
+                                     tally=args.tally_key_slots != 0, hot=args.hot_min != 0)
             svc.co = be.start(args.max_batch, int(args.gc_interval_ms * 1e6), args.gc_margin_ms,
-                              args.tally_key_slots)
+                              args.tally_key_slots, **hot)
             serve(svc, args.address, args.workers, ready=lambda p: print(f"READY {p}", flush=True))
     finally:
         be.close()

@@ -94,6 +94,15 @@ typedef struct rl_coalescer_opts {
      * every launched batch of requests is counted behind its decisions (a
      * caller compiled before this field passes the shorter struct_size: off) */
     uint32_t tally_key_slots;
+    /* Top keys (rl_hot_*, rl_engine.h): hot_min == 0 = off; otherwise
+     * rl_hot_opts' width, key_slots, weight and hot_min, and every launched
+     * batch of requests is counted behind its decisions, after the tally when
+     * both are on (a caller compiled before these fields passes a shorter
+     * struct_size: off) */
+    uint32_t hot_width;
+    uint32_t hot_key_slots;
+    uint32_t hot_weight;
+    uint64_t hot_min;
 } rl_coalescer_opts;
 
 typedef struct rl_coalescer_stats {
@@ -252,6 +261,19 @@ int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out);
 int rl_coalescer_tally(rl_coalescer* c, rl_tally_cfg* cfg_out, size_t cfg_cap, uint32_t* ncfg,
                        rl_tally_key* key_out, size_t key_cap, uint64_t* keys_tracked,
                        rl_tally_info* info, int clear);
+/* The top keys (rl_hot_read's arguments, rl_engine.h) in sequence order like
+ * rl_coalescer_tally: it has counted every request submitted before the call
+ * and none submitted after; nothing is drained.  With hot_min the submitter
+ * enqueues rl_hot_batch_device behind every batch of requests, on that batch's
+ * stream and arrays (behind the tally's, when that is on too; the slot's
+ * buffers are not reused before it has run): one rl_hot_batch call per launched
+ * batch.  Peeks and resets are not counted, nor are requests dropped unapplied
+ * (deadline, cancel).  Blocks until done.  RL_EINVAL when hot_min was 0.
+ * Over a host backend the coalescer keeps the same sketch and candidate table
+ * itself, on the host: per backend batch all the adds, then the look at the
+ * batch's keys.  A config id counts as known by the tally's host rule. */
+int rl_coalescer_hot(rl_coalescer* c, rl_hot_key* key_out, size_t key_cap, uint64_t* keys_tracked,
+                     rl_hot_info* info, int clear);
 
 #ifdef __cplusplus
 }

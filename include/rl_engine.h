@@ -336,6 +336,95 @@ int rl_tally_read(rl_engine* e, rl_tally_cfg* cfg_out, size_t cfg_cap, uint32_t*
  * block size); a larger batch strides */
 int rl_tally_grid_cap(void);
 
+/* Top keys: which keys carry the traffic, over all decisions -- a count-min
+ * sketch of RL_HOT_DEPTH rows by `width` 64-bit counters, plus a table of
+ * key_slots candidate keys.  A sibling of the tally: off until rl_hot_enable,
+ * it reads finished batches' arrays only and never touches the state tables,
+ * rl_stats, the sticky status of rl_engine_sync or the tally.  Every rl_hot_*
+ * call before rl_hot_enable is RL_EINVAL.
+ *
+ * A request (key_id, cfg_id, n, decision) counts iff cfg_id is registered,
+ * decision <= RL_ERROR (denied, allowed or error: the limiter executed it),
+ * key_id != RL_KEY_RESERVED and, with RL_HOT_UNITS, n > 0.  Its weight is 1
+ * (RL_HOT_REQUESTS) or (uint64_t)n (RL_HOT_UNITS); sums are modulo 2^64.
+ * Every other request adds 1 to `skipped` and nothing else.  `total` is the
+ * sum of the counted weights.
+ *
+ * The column of key k in row r (0 .. 3) is mix64(k ^ mix64(r + 1)) & (width - 1),
+ * mix64 as in the state tables (csrc/rl_table.h).  One rl_hot_batch(_device)
+ * call has exactly this effect:
+ *   (A) every counted request adds its weight to its four counters;
+ *   (B) once all of the call's adds are in, every key with a counted request
+ *       in this call is looked at: its estimate is the minimum of its four
+ *       counters, and if that is at least hot_min the key is inserted into the
+ *       candidate table.
+ * The candidate table follows the tally's rule: home slot mix64(k) &
+ * (key_slots - 1), linear probing over at most min(key_slots, 64) slots, an
+ * empty slot claimed with one CAS, the record keeps the cfg_id of one of the
+ * key's requests, and records are never released before a clear -- a key finds
+ * its record every time or finds its run taken every time.  A qualifying key
+ * without a slot makes `dropped` non-zero: it is non-zero exactly when that has
+ * happened since the last clear, its value is otherwise unspecified.
+ *
+ * Adds commute, so the sketch after a call is a function of the multiset of
+ * requests counted so far and, unless the table overflows, so is the candidate
+ * set: every key k for which some call held a counted request of k and left
+ * k's estimate at or above hot_min.  A count-min sketch never underestimates:
+ * every key whose true weight reaches hot_min is a candidate from the call in
+ * which it gets there.  Keys whose counters collide with heavier ones may be
+ * candidates too (false positives), with the overestimate they had.
+ *
+ * Error bound (documented, not tested): under the usual hashing assumption,
+ * estimate - true weight <= e * total / width for one key with probability at
+ * least 1 - e^-4. */
+#define RL_HOT_DEPTH 4
+#define RL_HOT_REQUESTS 0u
+#define RL_HOT_UNITS 1u
+typedef struct rl_hot_opts {
+    uint32_t struct_size;   /* sizeof(rl_hot_opts) */
+    uint32_t width;         /* rounded up to a power of 2, 16 .. 1<<24; 0 = 1<<18 */
+    uint32_t key_slots;     /* rounded up to a power of 2, 16 .. 1<<24; 0 = 65536 */
+    uint32_t weight;        /* RL_HOT_REQUESTS | RL_HOT_UNITS */
+    uint64_t hot_min;       /* >= 1, else RL_EINVAL */
+} rl_hot_opts;
+typedef struct rl_hot_key {
+    uint64_t key_id, estimate;
+    uint32_t cfg_id, pad_;  /* cfg_id: the config of one of the key's counted requests */
+} rl_hot_key;
+typedef struct rl_hot_info {
+    uint32_t struct_size, pad_;   /* sizeof(rl_hot_info) */
+    uint64_t width, depth, key_slots, hot_min, weight;
+    uint64_t keys_tracked, dropped, total, skipped;
+    uint64_t batches, requests;   /* rl_hot_batch(_device) calls with m > 0 / their requests */
+} rl_hot_info;
+/* allocates and zeroes the sketch and the table; a second call is RL_EINVAL.
+ * A config registered later counts from then on. */
+int rl_hot_enable(rl_engine* e, const rl_hot_opts* opts);
+/* Count one finished batch in the decide layout (device pointers), on `stream`
+ * (a hipStream_t; NULL = the engine's stream): two launches, the adds and then
+ * the look at the call's keys.  Queued after rl_decide_batch_device on the same
+ * stream it sees that batch's results.  The arrays must stay unmodified until
+ * the stream has passed the call.  m may exceed max_batch; m == 0 is RL_OK
+ * without a launch; null arrays with m > 0 are RL_EINVAL.  Calls on different
+ * streams may run at once; (B) of a call then sees what has been added by then. */
+int rl_hot_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const uint32_t* cfg_id,
+                        const int64_t* n, const uint8_t* decision, void* stream);
+/* the same with host arrays; synchronous */
+int rl_hot_batch(rl_engine* e, size_t m, const uint64_t* key_id, const uint32_t* cfg_id,
+                 const int64_t* n, const uint8_t* decision);
+/* Synchronous: waits for every rl_hot_* call made before it, on any stream.
+ * Each candidate's estimate is read from the sketch as it is now (a kernel over
+ * the candidate records; the sketch is not copied to the host).  Writes the
+ * key_cap candidates with the largest estimates, ordered by estimate
+ * descending, then key_id ascending (fewer when fewer are tracked;
+ * *keys_tracked: how many are).  Every output is nullable.  With clear != 0 the
+ * sketch, the candidates and the counters are zeroed before any later call. */
+int rl_hot_read(rl_engine* e, rl_hot_key* key_out, size_t key_cap, uint64_t* keys_tracked,
+                rl_hot_info* info, int clear);
+/* requests one k_hot_add / k_hot_pick launch covers with one request per thread
+ * (grid cap x block size); a larger batch strides */
+int rl_hot_grid_cap(void);
+
 #ifdef __cplusplus
 }
 #endif
