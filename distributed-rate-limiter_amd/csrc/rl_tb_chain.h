@@ -169,8 +169,10 @@ struct ChainShared {
     ChState st[2];
     ChSpec spec[2];                    // producers' speculative window of the round
     ChWin win[2];                      // the representation of tile[buf]'s window
-    double plan_s[CH_NP], plan_sp[CH_NP];   // ch_plan_par: each producer wave's tile sums
-    uint32_t plan_tag[CH_NP];               // and the plan number they belong to (0 at kernel start)
+    // ch_plan_par: each producer wave's tile sums and the plan number they
+    // belong to (0 at kernel start), in the slot of the plan number's parity
+    double plan_s[2][CH_NP], plan_sp[2][CH_NP];
+    uint32_t plan_tag[2][CH_NP];
 #ifdef RL_STAMPS
     uint32_t wk[2];                    // the round's longest producer work (cycles / 16)
 #endif
@@ -678,6 +680,13 @@ __device__ __attribute__((always_inline)) inline void ch_produce(ChainShared& sh
 // steps that follow an allow or a balance <= 0, decides the decade E.  A
 // guess: the chain adopts the window only if its exact replay agrees
 // (ch_segment).
+// floor(log10 x), out of line.  Inlined into ch_predict, log10's polynomial
+// constants were hoisted out of the round loop and held in VGPRs through the
+// whole kernel, for a step the guess reaches only when it has found an exit.
+// Same function, same result; k_tb_chain's own registers went from 256 to 248
+// and configs[1] from 3.22-3.25 to 3.28-3.30e9 (profiles/r7a_ab_log10_ool.txt).
+__device__ __attribute__((noinline)) int ch_floor_log10(double x) { return (int)floor(log10(x)); }
+
 __device__ __attribute__((always_inline)) inline ChSpec ch_predict(const ChainShared& sh, const ChState& s, double P,
                                                                   double R, uint32_t j1, bool xd) {
     constexpr int K = CH_K;
@@ -770,7 +779,7 @@ __device__ __attribute__((always_inline)) inline ChSpec ch_predict(const ChainSh
         if (first >= j1) return sp;
     }
     if (!(post < 1e12)) return sp;
-    const int e0 = (int)floor(log10(post));
+    const int e0 = ch_floor_log10(post);
 #pragma unroll
     for (int d = -1; d <= 1; d++) {
         const int e = e0 + d, k = 13 - e;
@@ -1841,6 +1850,10 @@ __device__ __attribute__((always_inline)) inline void ch_segment(ChainShared& sh
                     uint64_t tq0, tq1;
                     CH_T(tq0);
 #endif
+                    // (the round's second plan at most: the call above may have
+                    // made one and found no fit, and the round barrier comes
+                    // before the next -- the hand-off slots of ch_plan_par,
+                    // indexed by the plan number's parity, rely on it)
                     pl = ch_plan_w(shl, wf, wc, st_value(Xe, s.E, s.mode), pw, ++plan_seq);
 #ifdef RL_STAMPS
                     CH_T(tq1);
@@ -2225,7 +2238,7 @@ __global__ __launch_bounds__(CH_BLOCK) void k_tb_chain(const uint32_t* __restric
     const uint32_t nhuge = L.count[3];
     if (blockIdx.x == 0 && threadIdx.x == 0 && h_huge) *(volatile uint32_t*)h_huge = nhuge;
     if (!replay_joins(L, grid_base, light_min)) return;
-    if (threadIdx.x < (uint32_t)CH_NP) sh.plan_tag[threadIdx.x] = 0u;   // (the claim loop's barrier follows)
+    if (threadIdx.x < 2u * CH_NP) (&sh.plan_tag[0][0])[threadIdx.x] = 0u;   // (the claim loop's barrier follows)
     uint32_t plan_seq = 0;   // ch_plan_par numbers (the same in every producer wave)
     // timeline (10 ns ticks, low 32 bits): dbg[13] = ~first block start,
     // dbg[14] = last block end, dbg[16/17] = longest segment start / end

@@ -376,6 +376,12 @@ __device__ __attribute__((always_inline)) inline XPlan ch_plan_par(ChainShared& 
                                                                   double v0, uint32_t pw, uint32_t seq) {
     constexpr int K = CH_K;
     const uint32_t lane = threadIdx.x & 63;
+    // The hand-off slot is the plan number's parity.  A round makes at most
+    // two plans (ch_segment's two call sites) and the round barrier follows,
+    // so a wave still reading plan `seq` can only be overtaken by plan seq + 1,
+    // which writes the other slot: neither its sums nor its tags are
+    // overwritten before it has read them.
+    const uint32_t slot = seq & 1u;
     {
         double s = 0.0, sp = 0.0;
         double ra[K], rt[K];
@@ -391,16 +397,16 @@ __device__ __attribute__((always_inline)) inline XPlan ch_plan_par(ChainShared& 
         const double S = wave_reduce_f64(s, 0.0, [](double x, double y) { return x + y; });
         const double Sp = wave_reduce_f64(sp, 0.0, [](double x, double y) { return x + y; });
         if (lane == 0) {
-            sh.plan_s[pw] = S;
-            sh.plan_sp[pw] = Sp;
-            __hip_atomic_store(&sh.plan_tag[pw], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            sh.plan_s[slot][pw] = S;
+            sh.plan_sp[slot][pw] = Sp;
+            __hip_atomic_store(&sh.plan_tag[slot][pw], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
     bool ok = true;
 #pragma unroll
     for (int t = 0; t < CH_NP; t++) {
         uint32_t spins = 0;
-        while (__hip_atomic_load(&sh.plan_tag[t], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq) {
+        while (__hip_atomic_load(&sh.plan_tag[slot][t], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq) {
             if (++spins > (1u << 20)) { ok = false; break; }
             __builtin_amdgcn_s_sleep(1);
         }
@@ -411,7 +417,7 @@ __device__ __attribute__((always_inline)) inline XPlan ch_plan_par(ChainShared& 
 #pragma unroll
     for (int t = 0; t < CH_NP; t++) {
         pl.vt[t] = v;
-        const double S = sh.plan_s[t], Sp = sh.plan_sp[t];
+        const double S = sh.plan_s[slot][t], Sp = sh.plan_sp[slot][t];
         hi = fmax(hi, v + Sp);
         lo = fmin(lo, v - (Sp - S));
         v += S;
