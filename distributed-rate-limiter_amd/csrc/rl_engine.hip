@@ -570,6 +570,8 @@ static void free_all(rl_engine* e) {
     if (e->ev_small) (void)hipEventDestroy(e->ev_small);
     if (e->ev_reset) (void)hipEventDestroy(e->ev_reset);
     if (e->ev_peek) (void)hipEventDestroy(e->ev_peek);
+    (void)hipFree(e->d_refund);
+    if (e->ev_refund) (void)hipEventDestroy(e->ev_refund);
     for (void* p : {(void*)e->s_ts, (void*)e->s_n, (void*)e->s_sms, (void*)e->s_cfg, (void*)e->s_dec, (void*)e->s_tok,
                     (void*)e->s_add, (void*)e->s_th})
         (void)hipFree(p);

@@ -192,6 +192,13 @@ struct rl_engine {
     uint32_t hot_weight = 0;
     uint64_t hot_batches = 0, hot_requests = 0;
 
+    // refund scratch (rl_refund.h): one allocation, made and zeroed on `chain`
+    // by the first refund; refund_calls picks the list counter of a call
+    void* d_refund = nullptr;
+    uint64_t refund_records = 0;
+    uint64_t refund_calls = 0;
+    hipEvent_t ev_refund = nullptr;   // rl_refund_batch_device: k_refund_apply on `chain` -> the caller's stream
+
     // The tally's and the top keys' kernels run on the caller's stream and read
     // the feature's own memory: the end of the last such call on each stream
     // one was enqueued on is what drain(), rl_tally_read and rl_hot_read wait

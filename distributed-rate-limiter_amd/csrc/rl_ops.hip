@@ -1,6 +1,7 @@
-// rl_ops.hip -- Peek and Reset (single, batched, routed): the kernels of
-// rl_peek.h and rl_reset.h and their C entry points.  Each is one kernel on
-// the engine's `chain` stream between two replays (chain_op, rl_engine_impl.h).
+// rl_ops.hip -- Peek and Reset (single, batched, routed) and Refund: the
+// kernels of rl_peek.h, rl_reset.h and rl_refund.h and their C entry points.
+// Each is one chain op -- one kernel, Refund's two -- on the engine's `chain`
+// stream between two replays (chain_op, rl_engine_impl.h).
 // A code object of its own: that of the decision kernels (rl_engine.hip) does
 // not change with it.
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 #include "../../include/rl_route.h"
 #include "rl_engine_impl.h"
 #include "rl_peek.h"
+#include "rl_refund.h"
 #include "rl_reset.h"
 
 using namespace rl;
@@ -203,3 +205,90 @@ extern "C" int rl_peek_batch(rl_engine* e, size_t m, const uint64_t* key_id, con
 }
 
 extern "C" int rl_peek_grid_cap(void) { return PEEK_GRID * PEEK_BLOCK; }
+
+// --- Refund (rl_refund.h) ----------------------------------------------------
+
+static uint32_t refund_max(const rl_engine* e) { return std::min<uint32_t>(e->max_batch, REFUND_MAX); }
+
+// the engine's refund scratch, allocated and zeroed in-stream by the first
+// call: twice as many records as the largest call has requests, the claim
+// words, the records, the list and its two counters in one allocation
+static int refund_scratch(rl_engine* e, RefundScratch* out) {
+    if (!e->d_refund) {
+        const uint64_t R = 2 * pow2_at_least(refund_max(e));
+        const size_t bytes = R * (sizeof(refund_u64) + sizeof(RefundRec) + sizeof(uint32_t)) + 2 * sizeof(uint32_t);
+        if (!e->ev_refund) HIPCHK(e, hipEventCreateWithFlags(&e->ev_refund, hipEventDisableTiming));
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) return fail(e, RL_ENOMEM, "refund scratch: out of device memory");
+        if (hipMemsetAsync(p, 0, bytes, e->chain) != hipSuccess) {
+            (void)hipFree(p);
+            return fail(e, RL_EDEVICE, "refund scratch: memset failed");
+        }
+        e->d_refund = p;
+        e->refund_records = R;
+    }
+    const uint64_t R = e->refund_records;
+    char* p = (char*)e->d_refund;
+    out->loc = (refund_u64*)p;
+    out->rec = (RefundRec*)(p + R * sizeof(refund_u64));
+    out->list = (uint32_t*)(p + R * (sizeof(refund_u64) + sizeof(RefundRec)));
+    out->cnt = out->list + R;
+    out->mask = R - 1;
+    return RL_OK;
+}
+
+// enqueue one refund call of m <= refund_max requests: k_refund_add and
+// k_refund_apply as one chain op, where rl_reset_batch_device puts its kernel;
+// s waits for them.  Nothing is counted in rl_stats and no error flag is raised.
+static int run_refund(rl_engine* e, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                      const uint32_t* cfg, const int64_t* sms, uint8_t* status, hipStream_t s, bool inputs_ready) {
+    if (m == 0) return RL_OK;
+    RefundScratch S;
+    const int r = refund_scratch(e, &S);
+    if (r != RL_OK) return r;
+    const uint32_t parity = (uint32_t)(e->refund_calls++ & 1);
+    const uint32_t ncfg = (uint32_t)e->h_cfg.size();
+    return chain_op(e, s, inputs_ready, s, e->ev_refund, nullptr, [&](hipStream_t c) {
+        const int grid = grid_for(m, REFUND_BLOCK, REFUND_GRID);
+        k_refund_add<<<grid, REFUND_BLOCK, 0, c>>>((uint64_t)m, key, ts, n, cfg, sms, status, e->d_cfg, ncfg, e->d_tb,
+                                                   e->tb_cap - 1, e->d_win, e->win_cap - 1, e->spill(), e->profile, S,
+                                                   parity);
+        k_refund_apply<<<grid, REFUND_BLOCK, 0, c>>>(e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1,
+                                                     e->spill(), e->profile, S, parity);
+    });
+}
+
+extern "C" uint32_t rl_refund_max(rl_engine* e) { return e ? refund_max(e) : 0; }
+
+extern "C" int rl_refund_grid_cap(void) { return REFUND_GRID * REFUND_BLOCK; }
+
+// One refund call (rl_refund.h), ordered as rl_reset_batch_device.  Never
+// split: the sum rule holds per call.
+extern "C" int rl_refund_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                      const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                                      uint8_t* status, void* stream) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id))) return RL_EINVAL;
+    if (m > refund_max(e)) return fail(e, RL_EINVAL, "refund call above rl_refund_max");
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    return run_refund(e, m, key_id, ts_ns, n, cfg_id, server_ms, status, s, (e->flags & RL_OPT_PIPELINE) != 0);
+}
+
+extern "C" int rl_refund_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                               const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* status) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id))) return RL_EINVAL;
+    if (m > refund_max(e)) return fail(e, RL_EINVAL, "refund call above rl_refund_max");
+    if (m == 0) return RL_OK;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    // one chunk: m <= max_batch, the size of the host API's staging arrays
+    int r = stage_in(e, 0, (uint32_t)m, key_id, ts_ns, n, cfg_id, server_ms, s);
+    // the staged inputs arrive on s: the kernels always wait for them
+    if (r == RL_OK)
+        r = run_refund(e, m, e->d_key, e->d_ts, e->d_n, e->d_cfgid, server_ms ? e->d_sms : nullptr,
+                       status ? e->d_dec : nullptr, s, false);
+    if (r == RL_OK) r = stage_out(e, 0, (uint32_t)m, status, nullptr, nullptr, nullptr, nullptr, s);
+    if (r != RL_OK) return r;
+    HIPCHK(e, hipStreamSynchronize(s));
+    return RL_OK;
+}

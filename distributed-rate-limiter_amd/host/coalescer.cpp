@@ -209,6 +209,34 @@ public:
         ok &= hipEventRecord(d.ev, os_) == hipSuccess;
         return ok ? RL_OK : RL_EDEVICE;
     }
+    int launch_refund(int i, Slot& s) override {
+        (void)hipSetDevice(dev_id_);   // the submitter thread
+        Dev& d = dev_[i];
+        const size_t m = s.m;
+        // two kernels on the engine's replay stream between two batches; the
+        // output stream (and so this slot's completion event) waits for them
+        if (m <= zero_copy_max_) {
+            s.t_h2d = steady_ns();
+            const int rc = rl_refund_batch_device(e_, m, s.key, s.ts, s.n, s.cfg, nullptr, s.dec, os_);
+            if (rc != RL_OK) return rc;
+            return hipEventRecord(d.ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
+        }
+        Slot dv;
+        carve(d.key, M_, dv);
+        bool ok = hipMemcpyAsync(dv.key, s.key, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+        ok &= hipMemcpyAsync(dv.ts, s.ts, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+        ok &= hipMemcpyAsync(dv.n, s.n, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+        ok &= hipMemcpyAsync(dv.cfg, s.cfg, 4 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+        ok &= hipEventRecord(d.ev_in, cs_) == hipSuccess;
+        ok &= await_event(d.ev_in) == hipSuccess;
+        if (!ok) return RL_EDEVICE;
+        s.t_h2d = steady_ns();
+        const int rc = rl_refund_batch_device(e_, m, dv.key, dv.ts, dv.n, dv.cfg, nullptr, dv.dec, os_);
+        if (rc != RL_OK) return rc;
+        ok = hipMemcpyAsync(s.dec, dv.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
+        ok &= hipEventRecord(d.ev, os_) == hipSuccess;
+        return ok ? RL_OK : RL_EDEVICE;
+    }
     int wait(int i, Slot&) override {
         (void)hipSetDevice(dev_id_);   // the completer thread
         return await_event(dev_[i].ev) == hipSuccess ? RL_OK : RL_EDEVICE;
@@ -543,6 +571,10 @@ public:
         s.t_h2d = steady_ns();
         return b_.peek ? b_.peek(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset) : RL_EINVAL;
     }
+    int launch_refund(int, Slot& s) override {
+        s.t_h2d = steady_ns();
+        return b_.refund ? b_.refund(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec) : RL_EINVAL;
+    }
     int wait(int, Slot&) override { return RL_OK; }
     int table_info(int64_t now_ms, rl_table_info* out) override {
         return b_.table_info ? b_.table_info(b_.user, now_ms, out) : RL_EINVAL;
@@ -637,6 +669,8 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
                       uint64_t* ticket, int64_t deadline, void* tag, Op op) {
     if (!ticket || (m && (!key || !ts || !cfg || (!n && op != OP_RESET))) || deadline < 0 || !is_batched(op))
         return RL_EINVAL;
+    // a refund submission is one launch: never split (the engine's sum rule)
+    if (op == OP_REFUND && m > o_.max_batch) return RL_EINVAL;
     Sub* s = get_sub(m);
     s->op = op;
     s->deadline = deadline;
@@ -811,7 +845,7 @@ int Coalescer::Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* 
     // done and applied: no slot or queue references it any more
     lk.unlock();
     const size_t m = s->m;
-    if (s->op == OP_RESET) {
+    if (s->op == OP_RESET || s->op == OP_REFUND) {
         if (dec) memcpy(dec, s->dec, m);   // the per-request status
     } else if (has_requests(s->op)) {
         if (dec) memcpy(dec, s->dec, m);
@@ -1033,6 +1067,7 @@ void Coalescer::submitter() {
         // one launch, enqueued between the batches around it
         s.is_reset = f->op == OP_RESET;
         s.is_peek = f->op == OP_PEEK;
+        s.is_refund = f->op == OP_REFUND;
         size_t m = 0;
         const int64_t now = steady_ns();
         while (m < o_.max_batch && !queue_.empty()) {
@@ -1043,8 +1078,10 @@ void Coalescer::submitter() {
                 maybe_free_locked(sub);
                 continue;
             }
-            // requests merge, and so do resets; a peek submission is launched on its own
-            if (sub->op != f->op || (s.is_peek && sub != f)) break;
+            // requests merge, and so do resets; a peek submission is launched
+            // on its own, and so is a refund submission (one engine call: the
+            // engine sums the refunds of a call per target)
+            if (sub->op != f->op || ((s.is_peek || s.is_refund) && sub != f)) break;
             if (sub->taken < sub->m && (sub->cancelled || (sub->deadline && sub->deadline <= now))) {
                 // its context ended before (the rest of) it was sent: that part is never applied
                 if (sub->taken == 0) drop_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
@@ -1087,6 +1124,9 @@ void Coalescer::submitter() {
         } else if (s.is_peek) {
             // inserts nothing: no part in the automatic GC's budgets
             s.status = be_->launch_peek(si, s);
+        } else if (s.is_refund) {
+            // inserts nothing either
+            s.status = be_->launch_refund(si, s);
         } else {
             auto_gc(s);
             s.status = be_->launch(si, s);
@@ -1096,6 +1136,8 @@ void Coalescer::submitter() {
         if (s.is_reset) {
             st_.batches++;          // a launch, but no request batch: max_batch_seen stays
             st_.reset_launches++;
+        } else if (s.is_refund) {
+            st_.refund_launches++;
         } else if (!s.is_peek) {
             st_.batches++;
             st_.max_batch_seen = std::max<uint64_t>(st_.max_batch_seen, m);
@@ -1129,7 +1171,8 @@ void Coalescer::completer() {
         const int64_t t_wait = trace_cap_ ? steady_ns() : 0;
         int st = s.status == RL_OK ? be_->wait(si, s) : s.status;
         uint64_t nreset = 0;
-        if (s.is_reset) {
+        if (s.is_reset || s.is_refund) {
+            // RL_RESET_DONE and RL_REFUND_DONE are the same code
             if (st == RL_OK) {
                 for (const auto& p : s.parts) memcpy(p.sub->dec + p.off, s.dec + p.at, p.count);
                 for (size_t i = 0; i < s.m; i++) nreset += s.dec[i] == RL_RESET_DONE;
@@ -1158,6 +1201,7 @@ void Coalescer::completer() {
             done_batches_++;
             if (s.is_peek) st_.peeked += s.m;
             else if (s.is_reset) st_.resets += nreset;
+            else if (s.is_refund) st_.refunds += nreset;
             else st_.decided += s.m;
             for (const auto& p : s.parts) {
                 Sub* sub = p.sub;
@@ -1222,10 +1266,11 @@ extern "C" int rl_coalescer_create(rl_engine* e, const rl_coalescer_opts* opts, 
 
 extern "C" int rl_coalescer_create_with_host_backend(const rl_coalescer_backend* be, const rl_coalescer_opts* opts,
                                                      rl_coalescer** out) {
-    // a caller compiled before `peek` / `reset_batch` were added passes the shorter struct
+    // a caller compiled before `peek` / `reset_batch` / `refund` were added passes the shorter struct
     if (!be || !out ||
         (be->struct_size != sizeof(rl_coalescer_backend) && be->struct_size != offsetof(rl_coalescer_backend, peek) &&
-         be->struct_size != offsetof(rl_coalescer_backend, reset_batch)))
+         be->struct_size != offsetof(rl_coalescer_backend, reset_batch) &&
+         be->struct_size != offsetof(rl_coalescer_backend, refund)))
         return RL_EINVAL;
     rl_coalescer_backend b{};
     memcpy(&b, be, be->struct_size);
@@ -1241,7 +1286,7 @@ extern "C" int rl_coalescer_create_with_backend(rl_batch_fn fn, void* user, cons
 
 extern "C" int rl_coalescer_create_with_backends(rl_batch_fn fn, rl_reset_fn reset_fn, void* user,
                                                  const rl_coalescer_opts* opts, rl_coalescer** out) {
-    rl_coalescer_backend b{sizeof(rl_coalescer_backend), fn, reset_fn, nullptr, nullptr, user, nullptr, nullptr};
+    rl_coalescer_backend b{sizeof(rl_coalescer_backend), fn, reset_fn, nullptr, nullptr, user, nullptr, nullptr, nullptr};
     return rl_coalescer_create_with_host_backend(&b, opts, out);
 }
 
@@ -1311,6 +1356,17 @@ extern "C" int rl_coalescer_reset_batch(rl_coalescer* c, size_t m, const uint64_
     if (!c) return RL_EINVAL;
     uint64_t t;
     int rc = c->c->Submit(m, key_id, ts_ns, nullptr, cfg_id, &t, 0, nullptr, rlc::OP_RESET);
+    if (rc != RL_OK) return rc;
+    return c->c->Wait(t, -1, status, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rl_coalescer_refund(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                   const int64_t* n, const uint32_t* cfg_id, uint8_t* status) {
+    if (!c) return RL_EINVAL;
+    // one submission is one launch: a larger one is not split (the sum rule)
+    if (m > c->c->MaxBatch()) return RL_EINVAL;
+    uint64_t t;
+    int rc = c->c->Submit(m, key_id, ts_ns, n, cfg_id, &t, 0, nullptr, rlc::OP_REFUND);
     if (rc != RL_OK) return rc;
     return c->c->Wait(t, -1, status, nullptr, nullptr, nullptr);
 }

@@ -38,6 +38,7 @@ struct Slot {
     size_t m = 0;
     bool is_reset = false;   // resets (a run of adjacent OP_RESET submissions): key / ts / cfg in, status in `dec`
     bool is_peek = false;    // read-only queries (one OP_PEEK submission, or a part of it)
+    bool is_refund = false;  // one whole OP_REFUND submission: key / ts / n / cfg in, status in `dec`
     int status = RL_OK;
     int64_t t_form = 0, t_h2d = 0, t_launched = 0;   // steady ns (batch trace)
     struct Part {
@@ -92,6 +93,9 @@ public:
     // read-only queries (rl_peek_batch_device) on the slot's staging arrays,
     // ordered and completed like a launch
     virtual int launch_peek(int slot, Slot& s) = 0;
+    // one refund call (rl_refund_batch_device) on the slot's s.m requests,
+    // ordered and completed like a launch; per-request status into s.dec
+    virtual int launch_refund(int slot, Slot& s) = 0;
     virtual int wait(int slot, Slot& s) = 0;     // until launch `slot` completed
     // synchronous table operations (the GPU engine drains its batches first)
     virtual int table_info(int64_t now_ms, rl_table_info* out) = 0;
@@ -115,12 +119,13 @@ public:
 std::unique_ptr<Backend> make_gpu_backend(rl_engine* e);
 std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b);
 
-enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT };
+enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_REFUND, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT };
 // submissions that carry requests and results (the rest carry one operation)
 inline bool has_requests(Op op) { return op == OP_REQ || op == OP_PEEK; }
 // submissions the submitter takes from the queue in parts of up to max_batch:
-// requests and results, or resets (key / ts / cfg) and their status in `dec`
-inline bool is_batched(Op op) { return op <= OP_PEEK; }
+// requests and results, or resets (key / ts / cfg) and their status in `dec`;
+// a refund submission is taken whole
+inline bool is_batched(Op op) { return op <= OP_REFUND; }
 // the synchronous table operations (run_table_op)
 inline bool is_table_op(Op op) { return op >= OP_INFO; }
 
@@ -191,7 +196,9 @@ public:
     // like a Reset and launched on their own (not merged with requests or
     // with other peeks); not counted in submitted / decided --, or OP_RESET:
     // m resets (n is not read), merged with the reset submissions next to it
-    // in the queue into one launch; Wait's `dec` receives their status
+    // in the queue into one launch; Wait's `dec` receives their status; or
+    // OP_REFUND: one refund call of m <= max_batch requests, launched whole
+    // and on its own; Wait's `dec` receives the status
     int Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
                uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr, Op op = OP_REQ);
     // a single Reset (an OP_RESET submission of one) / table count / table GC /
@@ -203,6 +210,8 @@ public:
     bool TallyOn() const { return o_.tally_key_slots != 0; }
     // rl_coalescer_opts.hot_min != 0
     bool HotOn() const { return o_.hot_min != 0; }
+    // the largest launch: a refund submission above it is refused
+    size_t MaxBatch() const { return o_.max_batch; }
     // Completion callback for submissions made with a tag: fn(user, ticket,
     // tag) runs once when the submission is done (applied, failed, or dropped
     // unapplied), on a coalescer thread (or the thread of a Cancel / Wait that

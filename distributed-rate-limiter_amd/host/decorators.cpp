@@ -61,6 +61,34 @@ void MetricsDecorator::BatchAllow(const Context& ctx, const std::vector<BatchReq
     for (const auto& o : *out) record(o.err, o.has_result ? &o.result : nullptr, 1, dt);
 }
 
+Error MetricsDecorator::RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
+                                   std::vector<uint8_t>* applied) {
+    std::vector<uint8_t> a;
+    Error e = inner_->RefundMany(ctx, reqs, now_ns, &a);
+    if (!e) {
+        std::lock_guard<std::mutex> g(mu_);
+        for (size_t i = 0; i < reqs.size(); i++) {
+            refunds_[a[i] ? 1 : 0]++;
+            if (a[i]) {
+                const uint64_t u = (uint64_t)reqs[i].n;
+                refunded_units_ = refunded_units_ + u < refunded_units_ ? UINT64_MAX : refunded_units_ + u;
+            }
+        }
+        if (applied) *applied = a;
+    }
+    return e;
+}
+
+uint64_t MetricsDecorator::Refunds(bool applied) const {
+    std::lock_guard<std::mutex> g(mu_);
+    return refunds_[applied ? 1 : 0];
+}
+
+uint64_t MetricsDecorator::RefundedUnits() const {
+    std::lock_guard<std::mutex> g(mu_);
+    return refunded_units_;
+}
+
 uint64_t MetricsDecorator::Count(bool allowed, const std::string& error) const {
     std::lock_guard<std::mutex> g(mu_);
     auto it = requests_.find({allowed, error});
@@ -97,6 +125,20 @@ std::string MetricsDecorator::Expose() const {
     snprintf(line, sizeof line, "rate_limiter_decision_seconds_count{algorithm=\"%s\"} %llu\n", alg.c_str(),
              (unsigned long long)observations_);
     s += line;
+    if (refunds_[0] || refunds_[1]) {
+        s += "# HELP rate_limiter_refunds_total Refund requests by whether the key had live state.\n"
+             "# TYPE rate_limiter_refunds_total counter\n";
+        for (int a = 0; a < 2; a++) {
+            snprintf(line, sizeof line, "rate_limiter_refunds_total{algorithm=\"%s\",applied=\"%s\"} %llu\n", alg.c_str(),
+                     a ? "true" : "false", (unsigned long long)refunds_[a]);
+            s += line;
+        }
+        s += "# HELP rate_limiter_refunded_units_total Units given back by applied refunds.\n"
+             "# TYPE rate_limiter_refunded_units_total counter\n";
+        snprintf(line, sizeof line, "rate_limiter_refunded_units_total{algorithm=\"%s\"} %llu\n", alg.c_str(),
+                 (unsigned long long)refunded_units_);
+        s += line;
+    }
     return s;
 }
 
@@ -138,6 +180,22 @@ Error LoggingDecorator::ResetAt(const Context& ctx, const std::string& key, int6
 Error LoggingDecorator::ResetManyAt(const Context& ctx, const std::vector<std::string>& keys, int64_t t) {
     Error e = inner_->ResetManyAt(ctx, keys, t);
     if (e) sink_(LogLevel::Error, "rate limiter reset error", {{"keys", std::to_string(keys.size())}, {"error", e.msg}});
+    return e;
+}
+
+Error LoggingDecorator::RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
+                                   std::vector<uint8_t>* applied) {
+    std::vector<uint8_t> a;
+    Error e = inner_->RefundMany(ctx, reqs, now_ns, &a);
+    if (e) {
+        sink_(LogLevel::Error, "rate limiter refund error",
+              {{"keys", std::to_string(reqs.size())}, {"error", e.msg}});
+        return e;
+    }
+    for (size_t i = 0; i < reqs.size(); i++)
+        sink_(LogLevel::Debug, "quota refunded",
+              {{"key", reqs[i].key}, {"n", std::to_string(reqs[i].n)}, {"applied", a[i] ? "true" : "false"}});
+    if (applied) *applied = a;
     return e;
 }
 

@@ -44,9 +44,15 @@ public:
     Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) override {
         return inner_->PeekN(ctx, key, n, now_ns, out);
     }
+    // counted under names of their own: refunds by `applied`, refunded units
+    Error RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
+                     std::vector<uint8_t>* applied) override;
     void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                     std::vector<BatchOutcome>* out) override;
     const Config& config() const override { return inner_->config(); }
+    // refunds counted so far: [0] without live state, [1] applied; units of the applied ones
+    uint64_t Refunds(bool applied) const;
+    uint64_t RefundedUnits() const;
 
     // rate_limiter_requests_total{algorithm,allowed,error} and
     // rate_limiter_decision_seconds (histogram), Prometheus text format
@@ -65,6 +71,8 @@ private:
     std::array<uint64_t, 13> hist_{};   // kBuckets + +Inf
     double sum_s_ = 0.0;
     uint64_t observations_ = 0;
+    uint64_t refunds_[2] = {0, 0};
+    uint64_t refunded_units_ = 0;       // saturates
 };
 
 enum class LogLevel { Debug = 0, Info = 1, Warn = 2, Error = 3 };
@@ -86,6 +94,9 @@ public:
     Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) override {
         return inner_->PeekN(ctx, key, n, now_ns, out);
     }
+    // "quota refunded" at Debug per request, "rate limiter refund error" at Error per failed call
+    Error RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
+                     std::vector<uint8_t>* applied) override;
     void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                     std::vector<BatchOutcome>* out) override;
     const Config& config() const override { return inner_->config(); }

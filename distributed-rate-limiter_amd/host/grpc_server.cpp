@@ -121,6 +121,7 @@ void put_msg(std::string& o, uint32_t field, const std::string& m) {   // an emb
 struct ReqMsg {
     std::string_view limiter, key;
     int64_t n = 0;
+    int64_t at = 0;   // RefundRequest.window_reset_at_unix_ns = 4 (no other request has a field 4)
 };
 bool parse_req(std::string_view m, ReqMsg* r) {
     Pb pb{(const uint8_t*)m.data(), (const uint8_t*)m.data() + m.size()};
@@ -130,6 +131,7 @@ bool parse_req(std::string_view m, ReqMsg* r) {
         if (f == 1 && wt == 2) r->limiter = pb.bytes();
         else if (f == 2 && wt == 2) r->key = pb.bytes();
         else if (f == 3 && wt == 0) r->n = (int64_t)pb.varint();
+        else if (f == 4 && wt == 0) r->at = (int64_t)pb.varint();
         else pb.skip(wt);
     }
     return pb.ok;
@@ -226,8 +228,8 @@ struct Conn;
 
 // K_PEEK: a read-only AllowN (rl_coalescer_peek); K_RESET_BATCH: many resets, one coalescer submission;
 // K_USAGE: RateLimiterMetrics.Usage, one rl_coalescer_tally; K_TOPKEYS: RateLimiterTopKeys.TopKeys, one
-// rl_coalescer_hot
-enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE, K_TOPKEYS };
+// rl_coalescer_hot; K_REFUND / K_REFUND_BATCH: RateLimiterRefund, one refund submission (rl_coalescer_refund)
+enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE, K_TOPKEYS, K_REFUND, K_REFUND_BATCH };
 // a queued read that writes into buffers its Rpc owns: not cancelled when its
 // client goes away, but detached and left to finish
 inline bool is_read(Kind k) { return k == K_USAGE || k == K_TOPKEYS; }
@@ -622,6 +624,31 @@ void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, c
         s->publish_watch(h.keys.data(), nk);     // this response's keys are watched from now on
         return respond_ok(c, st, msg);
     }
+    if (rpc.kind == K_REFUND) {
+        // a storage error is the RPC's error, never a fail-open answer (as Reset)
+        if (rc != RL_OK) return respond_err(c, st, GRPC_UNAVAILABLE, "failed to refund rate limit: engine status " + std::to_string(rc));
+        put_int(msg, 1, dec && dec[0] == RL_REFUND_DONE ? 1 : 0);   // RefundResponse.applied = 1
+        return respond_ok(c, st, msg);
+    }
+    if (rpc.kind == K_REFUND_BATCH) {
+        // RefundBatchResponse.results = 1: RefundResult {applied = 1, error = 2} per request
+        size_t j = 0;
+        std::string one;
+        for (const BatchItem& b : rpc.items) {
+            one.clear();
+            if (b.err == 1) put_bytes(one, 2, "unknown limiter " + py_repr(b.name));
+            else if (b.err == 2) put_bytes(one, 2, ERR_INVALID_N);
+            else {
+                if (rc != RL_OK) put_bytes(one, 2, "failed to refund rate limit: engine status " + std::to_string(rc));
+                else put_int(one, 1, dec && dec[j] == RL_REFUND_DONE ? 1 : 0);
+                j++;
+            }
+            put_varint(msg, (1u << 3) | 2);   // an empty result is an entry too
+            put_varint(msg, one.size());
+            msg += one;
+        }
+        return respond_ok(c, st, msg);
+    }
     if (rpc.kind == K_RESET_BATCH) {
         // ResetBatchResponse.errors = 1: one string per request, "" = done
         size_t j = 0;
@@ -704,8 +731,12 @@ void submit_rpc(Io* io, Conn* c, Stream* st, Rpc&& rpc, size_t m, const uint64_t
     if (rpc.kind == K_RESET) rc = s->co->SubmitOp(rlc::OP_RESET, key[0], ts[0], cfg[0], 0, 0, 0, &ticket, io);
     // like a Reset, a reset batch has no deadline: once queued it is applied
     else if (rpc.kind == K_RESET_BATCH) rc = s->co->Submit(m, key, ts, nullptr, cfg, &ticket, 0, io, rlc::OP_RESET);
+    // one RPC is one refund submission: one engine call, applied in sequence order; no deadline, as a reset
+    else if (rpc.kind == K_REFUND || rpc.kind == K_REFUND_BATCH)
+        rc = s->co->Submit(m, key, ts, n, cfg, &ticket, 0, io, rlc::OP_REFUND);
     else rc = s->co->Submit(m, key, ts, n, cfg, &ticket, rpc.deadline, io, rpc.kind == K_PEEK ? rlc::OP_PEEK : rlc::OP_REQ);
-    if (rpc.kind != K_PEEK && rpc.kind != K_RESET_BATCH) s->n_dec += m;   // a peek or a reset decides nothing
+    // a peek, a reset or a refund decides nothing
+    if (rpc.kind != K_PEEK && rpc.kind != K_RESET_BATCH && rpc.kind != K_REFUND && rpc.kind != K_REFUND_BATCH) s->n_dec += m;
     if (rc != RL_OK) {   // queue full / closed: the error branch at once
         finish_rpc(io, 0, rpc, rc, nullptr, nullptr, nullptr, nullptr);
         return;
@@ -767,6 +798,58 @@ void dispatch(Conn* c, Stream* st) {
         if (rpc.m == 0) return finish_rpc(io, 0, rpc, RL_OK, nullptr, nullptr, nullptr, nullptr);
         const size_t mm = rpc.m;
         return submit_rpc(io, c, st, std::move(rpc), mm, key.data(), ts.data(), nullptr, cfg.data());
+    }
+    if (p == "/ratelimiter.v1.RateLimiterRefund/Refund") {
+        ReqMsg r;
+        if (!parse_req(msg, &r)) return respond_err(c, st, GRPC_INTERNAL, "bad RefundRequest");
+        const Limiter* lim = s->find(r.limiter);
+        if (!lim) return respond_err(c, st, GRPC_NOT_FOUND, "unknown limiter " + py_repr(r.limiter));
+        if (r.n <= 0) return respond_err(c, st, GRPC_INVALID_ARGUMENT, ERR_INVALID_N);
+        // the time that picks the window: just inside the window whose reset
+        // time the client passes back, or now
+        const int64_t now = s->now();
+        const int64_t t = r.at ? r.at - 1 : now;
+        const uint64_t id = s->key_id(lim, r.key);
+        Rpc rpc{c, st->id, K_REFUND, now, 0, lim, {}, 1};
+        const int64_t n = r.n;
+        const uint32_t cfg = lim->cfg;
+        return submit_rpc(io, c, st, std::move(rpc), 1, &id, &t, &n, &cfg);
+    }
+    if (p == "/ratelimiter.v1.RateLimiterRefund/RefundBatch") {
+        // one refund submission per RPC (one engine call: refunds of one key and
+        // window are summed), completed through the ticket's notification
+        Rpc rpc{c, st->id, K_REFUND_BATCH, s->now(), 0, nullptr, {}, 0};
+        std::vector<uint64_t> key;
+        std::vector<int64_t> ts, n;
+        std::vector<uint32_t> cfg;
+        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
+        while (pb.more()) {
+            const uint64_t tag = pb.varint();
+            if ((tag >> 3) != 1 || (tag & 7) != 2) {
+                pb.skip((uint32_t)(tag & 7));
+                continue;
+            }
+            ReqMsg r;
+            if (!parse_req(pb.bytes(), &r) || !pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad RefundBatchRequest");
+            BatchItem it{s->find(r.limiter), r.n, 0, {}};
+            if (!it.lim) {
+                it.err = 1;
+                it.name = std::string(r.limiter);
+            } else if (r.n <= 0) {
+                it.err = 2;
+            } else {
+                key.push_back(s->key_id(it.lim, r.key));
+                ts.push_back(r.at ? r.at - 1 : rpc.t);
+                n.push_back(r.n);
+                cfg.push_back(it.lim->cfg);
+            }
+            rpc.items.push_back(std::move(it));
+        }
+        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad RefundBatchRequest");
+        rpc.m = key.size();
+        if (rpc.m == 0) return finish_rpc(io, 0, rpc, RL_OK, nullptr, nullptr, nullptr, nullptr);
+        const size_t mm = rpc.m;
+        return submit_rpc(io, c, st, std::move(rpc), mm, key.data(), ts.data(), n.data(), cfg.data());
     }
     if (p == "/ratelimiter.v1.RateLimiterMetrics/Usage") {
         if (!s->tally || !s->co->TallyOn()) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "usage tally is off");

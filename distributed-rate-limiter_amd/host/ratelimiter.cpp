@@ -368,6 +368,42 @@ public:
         return Error{};
     }
 
+    Error RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
+                     std::vector<uint8_t>* applied) override {
+        const size_t m = reqs.size();
+        for (const auto& r : reqs)
+            if (r.n <= 0) return ErrInvalidN;
+        if (applied) applied->assign(m, 0);
+        if (closed_.load())
+            return Error::New(Error::Other, "failed to refund rate limit: engine: client is closed");
+        if (ctx.cancelled.load()) return Error::New(Error::Other, "failed to refund rate limit: context canceled");
+        if (m == 0) return Error{};
+        const int64_t now = now_ns == INT64_MIN ? eng_->clock() : now_ns;
+        const int64_t clock = eng_->server_ms_override != INT64_MIN ? eng_->server_ms_override
+                                                                    : rl::floor_div(now, 1000000LL);
+        std::vector<uint64_t> id(m);
+        std::vector<int64_t> ts(m), n(m);
+        for (size_t i = 0; i < m; i++) {
+            // a name the interner has never seen has no state: any id without
+            // state gives its answer (PeekN does the same)
+            id[i] = UINT64_MAX - 1;
+            (void)eng_->Lookup(cfg_.FormatKey(reqs[i].key), &id[i]);
+            ts[i] = reqs[i].at_ns ? reqs[i].at_ns : now;
+            n[i] = reqs[i].n;
+        }
+        const std::vector<uint32_t> cfg(m, cfg_id_);
+        const std::vector<int64_t> sms(m, clock);
+        std::vector<uint8_t> status(m);
+        std::lock_guard<std::mutex> g(eng_->mu());
+        const int rc = rl_refund_batch(eng_->raw(), m, id.data(), ts.data(), n.data(), cfg.data(), sms.data(),
+                                       status.data());
+        if (rc != RL_OK)
+            return Error::New(Error::Other, "failed to refund rate limit: " + engine_error(eng_->raw(), rc));
+        if (applied)
+            for (size_t i = 0; i < m; i++) (*applied)[i] = status[i] == RL_REFUND_DONE;
+        return Error{};
+    }
+
     Error Close() override {
         closed_.store(true);
         return Error{};
@@ -738,6 +774,35 @@ extern "C" int rll_reset_many(rll_limiter* l, size_t m, const char* const* keys,
         return RLL_ERR_RESET;
     }
     return RLL_OK;
+}
+
+extern "C" int rll_refund_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens,
+                               const int64_t* n, const int64_t* at_ns, int64_t now_ns, uint8_t* applied, char* err,
+                               size_t errlen) {
+    if (!l || (m && (!keys || !keylens || !n))) return RLL_ERR_ARG;
+    for (size_t i = 0; i < m; i++)
+        if (!keys[i] && keylens[i]) return RLL_ERR_ARG;
+    std::vector<RefundRequest> reqs(m);
+    for (size_t i = 0; i < m; i++) {
+        reqs[i].key.assign(keys[i] ? keys[i] : "", keylens[i]);
+        reqs[i].n = n[i];
+        reqs[i].at_ns = at_ns ? at_ns[i] : 0;
+    }
+    std::vector<uint8_t> a;
+    const Error e = l->lim->RefundMany(Context::Background(), reqs, now_ns == RLL_NOW_WALL ? INT64_MIN : now_ns, &a);
+    if (e) {
+        put_err(err, errlen, e.msg);
+        return e.is == Error::InvalidN ? RLL_ERR_INVALID_N : RLL_ERR_REFUND;
+    }
+    if (applied)
+        for (size_t i = 0; i < m; i++) applied[i] = a[i];
+    return RLL_OK;
+}
+
+extern "C" int rll_refund_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int64_t now_ns, int64_t at_ns,
+                            uint8_t* applied, char* err, size_t errlen) {
+    if (!l || (!key && keylen)) return RLL_ERR_ARG;
+    return rll_refund_many(l, 1, &key, &keylen, &n, &at_ns, now_ns, applied, err, errlen);
 }
 
 extern "C" int rll_close(rll_limiter* l) {

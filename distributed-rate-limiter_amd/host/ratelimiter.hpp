@@ -138,6 +138,14 @@ struct BatchOutcome {
     bool has_result = false;
 };
 
+// one refund: n units back to `key`; at_ns picks the window (a window limiter
+// refunds the counter of the window at_ns lies in; 0 = the call's time)
+struct RefundRequest {
+    std::string key;
+    int64_t n = 1;
+    int64_t at_ns = 0;
+};
+
 class RateLimiter {
 public:
     virtual ~RateLimiter() = default;
@@ -155,6 +163,24 @@ public:
     // now_ns (INT64_MIN: the engine clock), changing nothing.  n == 0 asks how
     // much is left; n < 0 is ErrInvalidN.  A key never seen is not interned.
     virtual Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) = 0;
+    // Refund (new; rl_refund_batch): give back quota an admitted request did
+    // not use, as ONE engine call -- per key (and window) the sum of the n is
+    // returned in one step: a bucket gains min(capacity, tokens + N), a window
+    // counter loses N (deleted at zero).  now_ns (INT64_MIN: the engine clock)
+    // is the store clock.  Any n <= 0 is ErrInvalidN before any I/O.  A
+    // storage error is returned as an error, never a fail-open Result, as
+    // Reset does.  applied[i] (nullable): the key had live state to refund to
+    // (a fresh key is full anyway).  A key never seen is not interned.
+    virtual Error RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
+                             std::vector<uint8_t>* applied) = 0;
+    // one refund (a call of one)
+    Error RefundN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, int64_t at_ns,
+                  bool* applied) {
+        std::vector<uint8_t> a;
+        Error e = RefundMany(ctx, {RefundRequest{key, n, at_ns}}, now_ns, &a);
+        if (!e && applied) *applied = a[0] != 0;
+        return e;
+    }
     // request-coalescing path (new): one engine launch for many requests
     virtual void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                             std::vector<BatchOutcome>* out) = 0;

@@ -31,9 +31,11 @@ ALG_BY_NAME = {"token_bucket": TOKEN_BUCKET, "sliding_window": SLIDING_WINDOW, "
 PROFILE_REDIS7, PROFILE_MINIREDIS = 0, 1
 DENIED, ALLOWED, ERROR, INVALID = 0, 1, 2, 3
 RESET_DONE = 1   # per-request status of a reset batch (RL_RESET_DONE; RL_INVALID otherwise)
+REFUND_NOKEY, REFUND_DONE = 0, 1   # per-request status of a refund call (RL_REFUND_*; RL_INVALID otherwise)
 KEY_RESERVED = (1 << 64) - 1
 
 RLL_OK, RLL_ERR_INVALID_N, RLL_ERR_FAILED, RLL_ERR_CONFIG, RLL_ERR_RESET, RLL_ERR_ARG = 0, 1, 2, 3, 4, 5
+RLL_ERR_REFUND = 6
 NOW_WALL = -(1 << 63)
 SMS_DEFAULT = -(1 << 63)
 
@@ -166,7 +168,7 @@ class rl_coalescer_stats(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("pad_", C.c_uint32)] + [
         (k, C.c_uint64) for k in ("submitted", "decided", "batches", "max_batch_seen", "pending", "expired",
                                   "cancelled", "gc_runs", "gc_checks", "gc_failures", "peeked", "resets",
-                                  "reset_launches")]
+                                  "reset_launches", "refunds", "refund_launches")]
 
 
 vp = C.c_void_p
@@ -174,13 +176,15 @@ vp = C.c_void_p
 BATCH_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp)
 RESET_FN = C.CFUNCTYPE(C.c_int, vp, C.c_uint32, C.c_uint64, C.c_int64)
 RESET_BATCH_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp)
+REFUND_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp)
 INFO_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.POINTER(rl_table_info))
 GC_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(rl_table_info))
 
 
 class rl_coalescer_backend(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("batch", BATCH_FN), ("reset", RESET_FN), ("table_info", INFO_FN),
-                ("gc", GC_FN), ("user", vp), ("peek", BATCH_FN), ("reset_batch", RESET_BATCH_FN)]
+                ("gc", GC_FN), ("user", vp), ("peek", BATCH_FN), ("reset_batch", RESET_BATCH_FN),
+                ("refund", REFUND_FN)]
 
 _sig = {
     "rl_engine_create": (C.c_int, [C.POINTER(rl_opts), C.POINTER(vp)]),
@@ -197,6 +201,10 @@ _sig = {
     "rl_reset_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
     "rl_reset_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
     "rl_reset_grid_cap": (C.c_int, []),
+    "rl_refund_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp, vp]),
+    "rl_refund_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]),
+    "rl_refund_max": (C.c_uint32, [vp]),
+    "rl_refund_grid_cap": (C.c_int, []),
     "rl_tally_enable": (C.c_int, [vp, C.POINTER(rl_tally_opts)]),
     "rl_tally_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
     "rl_tally_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
@@ -249,6 +257,9 @@ _sig = {
     "rll_allow_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp, vp]),
     "rll_reset": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int64, C.c_char_p, C.c_size_t]),
     "rll_reset_many": (C.c_int, [vp, C.c_size_t, vp, vp, C.c_int64, C.c_char_p, C.c_size_t]),
+    "rll_refund_n": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, vp, C.c_char_p,
+                               C.c_size_t]),
+    "rll_refund_many": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, C.c_int64, vp, C.c_char_p, C.c_size_t]),
     "rll_close": (C.c_int, [vp]),
     "rll_free": (C.c_int, [vp]),
     "rll_new_allowed_result": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(rll_result)]),
@@ -266,6 +277,7 @@ _sig = {
     "rl_coalescer_create_with_host_backend": (C.c_int, [C.POINTER(rl_coalescer_backend), vp, C.POINTER(vp)]),
     "rl_coalescer_reset": (C.c_int, [vp, C.c_uint64, C.c_int64, C.c_uint32]),
     "rl_coalescer_reset_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
+    "rl_coalescer_refund": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
     "rl_coalescer_now_ns": (C.c_int64, []),
     "rl_coalescer_submit_deadline": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, C.c_int64, C.POINTER(C.c_uint64)]),
     "rl_coalescer_cancel": (C.c_int, [vp, C.c_uint64]),
@@ -337,6 +349,8 @@ OPT_PIPELINE = 1
 PEEK_GRID_CAP = lib.rl_peek_grid_cap()
 # the same of k_reset_batch
 RESET_GRID_CAP = lib.rl_reset_grid_cap()
+# the same of k_refund_add / k_refund_apply
+REFUND_GRID_CAP = lib.rl_refund_grid_cap()
 # the same of k_tally
 TALLY_GRID_CAP = lib.rl_tally_grid_cap()
 # the same of k_hot_add / k_hot_pick
@@ -531,6 +545,32 @@ class Engine:
         rc = lib.rl_reset_batch_device(self.h, m, key_p, ts_p, cfg_p, status_p, stream)
         if rc != RL_OK:
             raise EngineError(rc, self.last_error())
+
+    def refund(self, key, ts, n, cfg, server_ms=None, want_status=True):
+        """rl_refund_batch: one refund call -- per target (a bucket, or the
+        window counter key of ts) one script run with the sum of the n of the
+        requests that found it live -> the per-request status (REFUND_DONE,
+        REFUND_NOKEY, INVALID)"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        sms = None if server_ms is None else np.ascontiguousarray(server_ms, dtype=np.int64)
+        m = key.size
+        assert ts.size == m and n.size == m and cfg.size == m and (sms is None or sms.size == m)
+        status = np.empty(m, np.uint8) if want_status else None
+        rc = lib.rl_refund_batch(self.h, m, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), _ptr(sms), _ptr(status))
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        return status
+
+    def refund_device(self, m, key_p, ts_p, n_p, cfg_p, sms_p=None, status_p=None, stream=None):
+        rc = lib.rl_refund_batch_device(self.h, m, key_p, ts_p, n_p, cfg_p, sms_p, status_p, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def refund_max(self) -> int:
+        return lib.rl_refund_max(self.h)
 
     def tally_enable(self, key_slots=0):
         """rl_tally_enable: allocate the usage tally (key_slots: records of
@@ -993,6 +1033,36 @@ class RateLimiter:
         rc = lib.rll_reset_many(self.h, m, C.cast(arr, vp), _ptr(lens), now_ns, buf, 512)
         return None if rc == RLL_OK else buf.value.decode()
 
+    def refund_n(self, key, n=1, now_ns=NOW_WALL, at_ns=0):
+        """rll_refund_n: give n units back to `key`; at_ns picks the window (0
+        = now) -> (applied | None, error message | None, code)"""
+        buf = C.create_string_buffer(512)
+        kb = key.encode()
+        applied = C.c_uint8(0)
+        rc = lib.rll_refund_n(self.h, kb, len(kb), n, now_ns, at_ns, C.byref(applied), buf, 512)
+        if rc == RLL_OK:
+            return bool(applied.value), None, rc
+        return None, buf.value.decode(), rc
+
+    def refund_many(self, keys, n, at_ns=None, now_ns=NOW_WALL):
+        """rll_refund_many: m refunds as one engine call (refunds of one key
+        and window are summed) -> (applied [bool] | None, error message |
+        None, code)"""
+        m = len(keys)
+        kbs = [k.encode() for k in keys]
+        arr = (C.c_char_p * m)(*kbs)
+        lens = np.array([len(k) for k in kbs], np.uint64)
+        nn = np.ascontiguousarray(n, np.int64)
+        at = None if at_ns is None else np.ascontiguousarray(at_ns, np.int64)
+        assert nn.size == m and (at is None or at.size == m)
+        applied = np.zeros(m, np.uint8)
+        buf = C.create_string_buffer(512)
+        rc = lib.rll_refund_many(self.h, m, C.cast(arr, vp), _ptr(lens), _ptr(nn), _ptr(at), now_ns, _ptr(applied),
+                                 buf, 512)
+        if rc == RLL_OK:
+            return applied.astype(bool), None, rc
+        return None, buf.value.decode(), rc
+
     def close(self):
         lib.rll_close(self.h)
 
@@ -1028,8 +1098,8 @@ class Coalescer:
     into engine batches.  `engine` is an Engine (GPU) or, for the CPU tests of
     the batching logic, a Python function with rl_decide_batch's host-array
     signature (the test seam rl_coalescer_create_with_host_backend; `reset`,
-    `table_info`, `gc`, `peek`, `reset_batch`: the other backend functions,
-    optional).
+    `table_info`, `gc`, `peek`, `reset_batch`, `refund`: the other backend
+    functions, optional).
 
     gc_interval_ns > 0 turns on the automatic table GC (rl_coalescer_opts);
     tally_key_slots the usage tally; hot_min (with hot_width, hot_key_slots,
@@ -1038,7 +1108,7 @@ class Coalescer:
     def __init__(self, engine, max_batch=65536, max_in_flight=3, linger_ns=0, queue_cap=0, reset=None,
                  table_info=None, gc=None, peek=None, gc_interval_ns=0, gc_high_pct=0, gc_margin_ms=0,
                  gc_max_tb_capacity=0, gc_max_win_capacity=0, reset_batch=None, tally_key_slots=0, hot_min=0,
-                 hot_width=0, hot_key_slots=0, hot_weight=HOT_REQUESTS):
+                 hot_width=0, hot_key_slots=0, hot_weight=HOT_REQUESTS, refund=None):
         o = rl_coalescer_opts_hot(hot_min=hot_min, hot_width=hot_width, hot_key_slots=hot_key_slots, hot_weight=hot_weight,
                               max_batch=max_batch, max_in_flight=max_in_flight, gc_high_pct=gc_high_pct,
                               linger_ns=linger_ns, queue_cap=queue_cap, gc_interval_ns=gc_interval_ns,
@@ -1055,7 +1125,8 @@ class Coalescer:
                 table_info=INFO_FN(table_info) if table_info else C.cast(None, INFO_FN),
                 gc=GC_FN(gc) if gc else C.cast(None, GC_FN), user=None,
                 peek=BATCH_FN(peek) if peek else C.cast(None, BATCH_FN),
-                reset_batch=RESET_BATCH_FN(reset_batch) if reset_batch else C.cast(None, RESET_BATCH_FN))
+                reset_batch=RESET_BATCH_FN(reset_batch) if reset_batch else C.cast(None, RESET_BATCH_FN),
+                refund=REFUND_FN(refund) if refund else C.cast(None, REFUND_FN))
             rc = lib.rl_coalescer_create_with_host_backend(C.byref(self._be), C.byref(o), C.byref(h))
         if rc != RL_OK:
             raise EngineError(rc, "rl_coalescer_create failed")
@@ -1101,6 +1172,19 @@ class Coalescer:
         assert ts.size == key.size and cfg.size == key.size
         status = np.empty(key.size, np.uint8)
         rc = lib.rl_coalescer_reset_batch(self.h, key.size, _ptr(key), _ptr(ts), _ptr(cfg), _ptr(status))
+        return rc, status
+
+    def refund(self, key, ts, n, cfg):
+        """rl_coalescer_refund: one refund call as one submission in sequence
+        order, one launch, never merged or split; blocks until applied.
+        -> (rc, status): REFUND_DONE, REFUND_NOKEY or INVALID per request"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        assert ts.size == key.size and n.size == key.size and cfg.size == key.size
+        status = np.empty(key.size, np.uint8)
+        rc = lib.rl_coalescer_refund(self.h, key.size, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), _ptr(status))
         return rc, status
 
     def peek(self, key, ts, n, cfg):

@@ -219,6 +219,30 @@ def reset_batch(stub, pairs, **kw):
     return list(stub.ResetBatch(req, **kw).errors)
 
 
+def refund_stub(channel):
+    """the refund service (RateLimiterRefund: Refund, RefundBatch)"""
+    return Stub(channel, api("ratelimiter.proto"), "RateLimiterRefund")
+
+
+def refund(stub, limiter: str, key: str, n: int = 1, window_reset_at_unix_ns: int = 0, **kw) -> bool:
+    """RateLimiterRefund.Refund (stub: refund_stub(channel)): give n units back to `key`.  Pass the
+    reset_at_unix_ns of the Allow response being refunded to hit the window it charged (0: the window current now)
+    -> applied: the key had live state to give back to"""
+    a = api("ratelimiter.proto")
+    return stub.Refund(a.RefundRequest(limiter=limiter, key=key, n=n,
+                                       window_reset_at_unix_ns=window_reset_at_unix_ns), **kw).applied
+
+
+def refund_batch(stub, items, **kw):
+    """RateLimiterRefund.RefundBatch of (limiter, key, n[, window_reset_at_unix_ns]) tuples: one engine call ->
+    [(applied, error)] per item, error "" = done"""
+    a = api("ratelimiter.proto")
+    req = a.RefundBatchRequest(requests=[a.RefundRequest(limiter=i[0], key=i[1], n=i[2],
+                                                         window_reset_at_unix_ns=i[3] if len(i) > 3 else 0)
+                                         for i in items])
+    return [(r.applied, r.error) for r in stub.RefundBatch(req, **kw).results]
+
+
 def metrics_stub(channel):
     """the observability service (RateLimiterMetrics: Usage)"""
     return Stub(channel, api("ratelimiter.proto"), "RateLimiterMetrics")

@@ -330,6 +330,59 @@ class RateLimiterService:
                     errors[i] = f"failed to reset rate limit: engine status {rl_amd.RL_EINVAL}"
         return self.a.ResetBatchResponse(errors=errors)
 
+    @staticmethod
+    def _refund_ts(r, t):
+        """the time that picks the refund's window: just inside the window
+        whose reset time the client passes back, or now"""
+        return r.window_reset_at_unix_ns - 1 if r.window_reset_at_unix_ns else t
+
+    def Refund(self, req, ctx):
+        """give n units back (rl_coalescer_refund): one submission, applied in
+        sequence order.  Blocks like Reset; a storage error is the RPC's error,
+        never a fail-open answer."""
+        lim = self._limiter(req.limiter, ctx)
+        if req.n <= 0:
+            ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, ERR_INVALID_N)
+        rc, status = self.co.refund([self._key_id(lim, req.key)], [self._refund_ts(req, self.clock())], [req.n],
+                                    [lim.cfg_id])
+        if rc != rl_amd.RL_OK:
+            ctx.abort(grpc.StatusCode.UNAVAILABLE, f"failed to refund rate limit: engine status {rc}")
+        return self.a.RefundResponse(applied=int(status[0]) == rl_amd.REFUND_DONE)
+
+    def RefundBatch(self, req, ctx):
+        """many refunds: one refund submission to the coalescer (one engine
+        call: refunds of one key and window are summed); an unknown limiter or
+        n <= 0 is that entry's error string"""
+        rs = req.requests
+        t = self.clock()
+        out = [None] * len(rs)
+        idx, keys, cfg, ns, ts = [], [], [], [], []
+        groups = {}
+        for i, r in enumerate(rs):
+            lim = self.by_name.get(r.limiter)
+            if lim is None:
+                out[i] = self.a.RefundResult(error=f"unknown limiter {r.limiter!r}")
+            elif r.n <= 0:
+                out[i] = self.a.RefundResult(error=ERR_INVALID_N)
+            else:
+                groups.setdefault(r.limiter, []).append(len(idx))
+                idx.append(i)
+                keys.append(r.key.encode())
+                cfg.append(lim.cfg_id)
+                ns.append(r.n)
+                ts.append(self._refund_ts(r, t))
+        if idx:
+            kid = np.empty(len(idx), np.uint64)
+            for name, pos in groups.items():
+                kid[pos] = self._ids(self.by_name[name], [keys[p] for p in pos], len(pos))
+            rc, status = self.co.refund(kid, np.array(ts, np.int64), np.array(ns, np.int64), np.array(cfg, np.uint32))
+            for j, i in enumerate(idx):
+                if rc != rl_amd.RL_OK:
+                    out[i] = self.a.RefundResult(error=f"failed to refund rate limit: engine status {rc}")
+                else:
+                    out[i] = self.a.RefundResult(applied=int(status[j]) == rl_amd.REFUND_DONE)
+        return self.a.RefundBatchResponse(results=out)
+
     def AllowBatch(self, req, ctx):
         """many AllowN calls: one submission to the coalescer (one GPU batch
         when it fits); per-request errors in AllowResponse.error"""
@@ -378,7 +431,7 @@ def build_server(service: RateLimiterService, address: str, workers: int = 64) -
                          options=[("grpc.so_reuseport", 0)])
     for a, sname, impl in ((service.a, "RateLimiter", service), (service.a, "RateLimiterStatus", service),
                            (service.a, "RateLimiterAdmin", service), (service.a, "RateLimiterMetrics", service),
-                           (service.a, "RateLimiterTopKeys", service),
+                           (service.a, "RateLimiterTopKeys", service), (service.a, "RateLimiterRefund", service),
                            (service.h, "Health", service)):
         handlers = {}
         for mname, inp, out in a.services[sname]:

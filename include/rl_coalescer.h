@@ -121,6 +121,9 @@ typedef struct rl_coalescer_stats {
     uint64_t peeked;         /* read-only queries completed (rl_coalescer_peek); not in submitted / decided */
     uint64_t resets;         /* resets executed (rl_coalescer_reset / _reset_batch); not in submitted / decided */
     uint64_t reset_launches; /* launches they took: a run of adjacent reset submissions is one launch */
+    uint64_t refunds;        /* refund requests that contributed (RL_REFUND_DONE; rl_coalescer_refund); not in
+                                submitted / decided */
+    uint64_t refund_launches; /* refund submissions launched: one launch each, never merged */
 } rl_coalescer_stats;
 
 /* Signature of rl_decide_batch (host arrays, synchronous).  A backend of this
@@ -134,6 +137,10 @@ typedef int (*rl_reset_fn)(void* user, uint32_t cfg_id, uint64_t key_id, int64_t
 /* rl_reset_batch's signature: m resets, per-request status (RL_RESET_DONE / RL_INVALID; never null here) */
 typedef int (*rl_reset_batch_fn)(void* user, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
                                  const uint32_t* cfg_id, uint8_t* status);
+/* rl_refund_batch's signature without the store clock (floor(ts_ns / 1e6)): one refund call, per-request
+ * status (RL_REFUND_DONE / RL_REFUND_NOKEY / RL_INVALID; never null here) */
+typedef int (*rl_refund_fn)(void* user, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                            const uint32_t* cfg_id, uint8_t* status);
 /* table counts / GC for the host backend (rl_table_info_get / rl_table_gc) */
 typedef int (*rl_info_fn)(void* user, int64_t now_ms, rl_table_info* out);
 typedef int (*rl_gc_fn)(void* user, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
@@ -152,6 +159,8 @@ typedef struct rl_coalescer_backend {
                                 before this field passes the shorter struct_size: no peek) */
     rl_reset_batch_fn reset_batch; /* nullable (and absent from a shorter struct): resets then go through
                                       `reset`, one call per key; its RL_EINVAL is that request's RL_INVALID */
+    rl_refund_fn refund;     /* nullable (and absent from a shorter struct): rl_coalescer_refund is then
+                                RL_EINVAL */
 } rl_coalescer_backend;
 
 /* Coalescer over a GPU engine, on the device current on the calling thread
@@ -219,6 +228,21 @@ int rl_coalescer_reset(rl_coalescer* c, uint64_t key_id, int64_t ts_ns, uint32_t
  * the automatic GC's insert budgets (stats.resets, stats.reset_launches). */
 int rl_coalescer_reset_batch(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
                              const uint32_t* cfg_id, uint8_t* status);
+/* One refund call (rl_refund_batch_device, include/rl_engine.h; the store
+ * clock of a request is floor(ts_ns / 1e6)) as one submission in sequence
+ * order: after every request submitted before it, before every request
+ * submitted after it, on the engine's replay stream -- the pipeline is not
+ * drained.  Blocks until applied.  `status` (nullable): RL_REFUND_DONE,
+ * RL_REFUND_NOKEY or RL_INVALID per request.  A submission is one launch and
+ * one engine call: it is never split (larger than max_batch, or than the
+ * engine's rl_refund_max: RL_EINVAL) and never merged with another refund
+ * submission, since the engine sums the refunds of one call per target; the
+ * submissions apply in sequence order, so a caller who wants refunds applied
+ * one by one sends one per call.  Counted in stats.refunds /
+ * .refund_launches only; no part in the automatic GC's insert budgets.
+ * RL_EINVAL over a host backend without `refund`. */
+int rl_coalescer_refund(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                        const uint32_t* cfg_id, uint8_t* status);
 /* Read-only queries (rl_peek_batch_device, include/rl_engine.h): for each
  * request the Result AllowN would return, against the state left by every
  * request submitted before the call and none submitted after it; nothing is

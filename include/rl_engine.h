@@ -184,6 +184,53 @@ int rl_reset_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const 
  * x block size); a larger batch strides */
 int rl_reset_grid_cap(void);
 
+/* Refund: give consumed quota back.  A request is (key_id, ts_ns, n, cfg_id,
+ * server_ms): ts_ns selects the window (a window limiter refunds the counter
+ * key of window_start(ts_ns); a sliding window only that one, the previous
+ * window's count is history), server_ms (nullable: floor(ts_ns / 1e6)) is the
+ * store clock that decides whether the target is live.  One call groups its
+ * valid requests by target -- the bucket of key_id, or the window counter key
+ * wherever it lives -- and has the effect of one script run per target, with N
+ * the sum (saturated at INT64_MAX) of the n of the requests whose target is
+ * live at their own store clock in the state left by every batch enqueued
+ * before the call:
+ *   token bucket:  tokens = math.min(capacity, tokens + N), stored through
+ *                  tostring (%.14g under RL_PROFILE_REDIS7); last_refill and
+ *                  the TTL are untouched
+ *   window:        if count <= N then DEL key else DECRBY key N (TTL kept)
+ * The sum and not m single refunds: for a bucket %.14g requantises the stored
+ * count, so single refunds do not commute; a caller who needs them one by one
+ * sends one refund per call.  Per-request status (nullable), from the state
+ * before the call only:
+ *   RL_REFUND_DONE   the request contributed
+ *   RL_REFUND_NOKEY  valid, but its target has no live state (a fresh key is
+ *                    full anyway); nothing is stored for it: no insert and no
+ *                    lazy-expiry delete
+ *   RL_INVALID       n <= 0, unknown cfg_id or RL_KEY_RESERVED; the rest of the
+ *                    call is applied and the call returns RL_OK
+ * Two configs refunding one bucket id in one call use the capacity of one of
+ * them, unspecified.  m <= rl_refund_max(e) = min(max_batch, 1 << 20), else
+ * RL_EINVAL: a call is never split (the sum rule).  m == 0 is RL_OK without a
+ * launch; null input arrays with m > 0 are RL_EINVAL.  rl_stats.batches /
+ * .decisions, the sticky status of rl_engine_sync, the tally and the top keys
+ * are untouched.  Host arrays; synchronous. */
+#define RL_REFUND_NOKEY 0
+#define RL_REFUND_DONE  1
+int rl_refund_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                    const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* status);
+/* Same, with device pointers, ordered exactly as rl_reset_batch_device: two
+ * kernels on the engine's replay stream, after every batch enqueued before the
+ * call and before every batch enqueued after it, nothing drained; `stream`
+ * waits for them.  The first refund of an engine allocates its scratch. */
+int rl_refund_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                           const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* status,
+                           void* stream);
+/* the largest refund call */
+uint32_t rl_refund_max(rl_engine* e);
+/* refunds one launch covers with one request per thread (grid cap x block
+ * size); a larger call strides */
+int rl_refund_grid_cap(void);
+
 /* Peek: read-only quota queries.  For each request, the outputs
  * rl_decide_batch would give for it at (ts_ns, server_ms) against the state
  * left by every batch enqueued before the call -- and nothing changes: no key

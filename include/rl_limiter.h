@@ -27,6 +27,7 @@ extern "C" {
 #define RLL_ERR_CONFIG   3  /* constructor error ("config cannot be nil", "invalid config: ...") */
 #define RLL_ERR_RESET    4  /* fmt.Errorf("failed to reset rate limit: %w") */
 #define RLL_ERR_ARG      5  /* bad C argument */
+#define RLL_ERR_REFUND   6  /* fmt.Errorf("failed to refund rate limit: %w"), in Reset's style */
 
 #define RLL_NOW_WALL   INT64_MIN  /* now_ns: read the wall clock (time.Now()) */
 #define RLL_SMS_DEFAULT INT64_MIN /* server_ms: Redis clock = floor(now_ns / 1e6) */
@@ -121,6 +122,30 @@ int rll_reset(rll_limiter* l, const char* key, size_t keylen, int64_t now_ns, ch
  * RLL_ERR_RESET with the message of the failure. */
 int rll_reset_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens, int64_t now_ns,
                    char* err, size_t errlen);
+/* Refund: give n units back to `key` (rl_refund_batch, include/rl_engine.h):
+ * a bucket gains min(capacity, tokens + n), a window counter loses n and is
+ * deleted at zero.  now_ns is the store clock (RLL_NOW_WALL: the wall clock);
+ * at_ns picks the window a window limiter refunds -- the time of the request
+ * being refunded, or any time inside its window; 0 = now_ns.  *applied
+ * (nullable): 1 when the key had live state, 0 when it had none (never seen,
+ * expired, or that window holds nothing: a fresh key is full anyway, and
+ * nothing is stored or interned for it).  n <= 0 is RLL_ERR_INVALID_N with
+ * ErrInvalidN's text, before any I/O.  A storage error (a closed limiter, an
+ * engine failure) is RLL_ERR_REFUND with its message -- never a fail-open
+ * result, as Reset.  The metrics decorator counts refunds and refunded units
+ * (rate_limiter_refunds_total{algorithm,applied},
+ * rate_limiter_refunded_units_total{algorithm}; exposed once a refund was
+ * made); the logging decorator logs a refund at debug and its failure at
+ * error level. */
+int rll_refund_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int64_t now_ns, int64_t at_ns,
+                 uint8_t* applied, char* err, size_t errlen);
+/* RefundMany: m refunds as ONE engine call -- refunds of one key (and window)
+ * are summed and returned in one step, which for a token bucket under
+ * RL_PROFILE_REDIS7 can differ in the last digit from m rll_refund_n calls
+ * (%.14g requantises the stored count after each).  at_ns nullable (all 0).
+ * Any n <= 0 fails the whole call with RLL_ERR_INVALID_N, nothing applied. */
+int rll_refund_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens, const int64_t* n,
+                    const int64_t* at_ns, int64_t now_ns, uint8_t* applied, char* err, size_t errlen);
 int rll_close(rll_limiter* l);   /* Close(): later calls take the storage-error path */
 int rll_free(rll_limiter* l);
 
