@@ -10,6 +10,8 @@
 #include <algorithm>
 #include <chrono>
 
+#include "../csrc/rl_table.h"   // rl::mix64
+
 namespace rlc {
 
 int64_t steady_ns() {
@@ -18,10 +20,13 @@ int64_t steady_ns() {
         .count();
 }
 
-// per request: key 8 + ts 8 + n 8 + rem 8 + retry 8 + reset 8 + cfg 4 + dec 1
-Sub::Sub(size_t m_) : mem(new uint8_t[(m_ ? m_ : 1) * 53 + 8]), cap(m_ ? m_ : 1) { carve(m_); }
+Sub::Sub(size_t m_) : mem(new uint8_t[block_bytes(m_ ? m_ : 1)]), cap(m_ ? m_ : 1) {
+    // layout by capacity, so a reused buffer keeps its arrays in place
+    carve(mem.get(), cap, *this);
+    renew(m_);
+}
 
-void Sub::carve(size_t m_) {
+void Sub::renew(size_t m_) {
     first = 0;
     m = m_;
     taken = 0;
@@ -33,23 +38,8 @@ void Sub::carve(size_t m_) {
     inflight = 0;
     done_ns = submit_ns = 0;
     tag = nullptr;
-    now_ms = 0;
-    cap_tb = cap_win = 0;
+    args = OpArgs{};
     info = rl_table_info{};
-    snap = SnapArgs{};
-    tally = TallyArgs{};
-    hot = HotArgs{};
-    // layout by capacity, so a reused buffer keeps its arrays in place
-    const size_t c = cap;
-    uint8_t* p = mem.get();
-    key = reinterpret_cast<uint64_t*>(p);
-    ts = reinterpret_cast<int64_t*>(p + 8 * c);
-    n = reinterpret_cast<int64_t*>(p + 16 * c);
-    rem = reinterpret_cast<int64_t*>(p + 24 * c);
-    retry = reinterpret_cast<int64_t*>(p + 32 * c);
-    reset = reinterpret_cast<int64_t*>(p + 40 * c);
-    cfg = reinterpret_cast<uint32_t*>(p + 48 * c);
-    dec = p + 52 * c;
 }
 
 // Completion waits: the runtime's (default), or polling the event
@@ -97,12 +87,12 @@ public:
         for (int i = 0; i < nslots; i++) {
             // inputs first (one H2D block), then outputs
             void* h = nullptr;
-            if (hipHostMalloc(&h, M * 61 + 64, hipHostMallocDefault) != hipSuccess) return RL_ENOMEM;
+            if (hipHostMalloc(&h, block_bytes(M), hipHostMallocDefault) != hipSuccess) return RL_ENOMEM;
             host_.push_back(h);
             carve(static_cast<uint8_t*>(h), M, (*slots)[i]);
             Dev& d = dev_[i];
             uint8_t* dp = nullptr;
-            if (hipMalloc(&dp, M * 61 + 64) != hipSuccess) return RL_ENOMEM;
+            if (hipMalloc(&dp, block_bytes(M)) != hipSuccess) return RL_ENOMEM;
             d.key = dp;
             if (hipEventCreateWithFlags(&d.ev, hipEventDisableTiming) != hipSuccess) return RL_EDEVICE;
             if (hipEventCreateWithFlags(&d.ev_in, hipEventDisableTiming) != hipSuccess) return RL_EDEVICE;
@@ -110,8 +100,6 @@ public:
         M_ = M;
         return RL_OK;
     }
-    int launch(int i, Slot& s) override { return launch_on(i, s, rl_decide_batch_device, tally_, hot_); }
-    int launch_peek(int i, Slot& s) override { return launch_on(i, s, rl_peek_batch_device, false, false); }
     int tally_enable(uint32_t key_slots) override {
         (void)hipSetDevice(dev_id_);
         rl_tally_opts o{sizeof(rl_tally_opts), key_slots};
@@ -138,104 +126,69 @@ public:
         (void)hipSetDevice(dev_id_);
         return rl_hot_read(e_, a.key_out, a.key_cap, a.keys_tracked, a.info, a.clear);
     }
-    // rl_decide_batch_device / rl_peek_batch_device: one argument list
-    using DeviceFn = int (*)(rl_engine*, size_t, const uint64_t*, const int64_t*, const int64_t*, const uint32_t*,
-                             const int64_t*, uint8_t*, int64_t*, int64_t*, int64_t*, double*, void*);
-    // tally, hot: count the batch on os_ behind its results, on the arrays the
-    // decide used (the tally first); the slot's completion event is recorded
-    // behind them, so the slot is not reused before they have run
-    int launch_on(int i, Slot& s, DeviceFn fn, bool tally, bool hot) {
+    // The one staging routine.  A batch of up to zero_copy_max_ requests runs
+    // zero-copy: the kernels read the requests from, and write the results
+    // into, the pinned slot itself (host memory the device maps).  No
+    // hipMemcpyAsync on the submit path: the configs[4] stalls were the
+    // submitter blocked ~8 ms inside those calls with the device idle
+    // (profiles/r3d_stall_trace.json).  A larger one is staged: the inputs
+    // the operation reads go to the slot's device block on cs_ and are waited
+    // for here, and what it returns comes back on os_ behind the engine's
+    // work.  Either way the slot's completion event is recorded on os_ last,
+    // so the slot is not reused before everything enqueued for it has run.
+    int launch(int i, Slot& s) override {
         (void)hipSetDevice(dev_id_);   // the submitter thread
         Dev& d = dev_[i];
-        Slot dv;
-        carve(d.key, M_, dv);
+        const OpTraits& t = OPS[s.op];
         const size_t m = s.m;
-        if (m <= zero_copy_max_) {
-            // zero-copy: the kernels read the requests from, and write the
-            // results into, the pinned slot itself (host memory the device
-            // maps).  No hipMemcpyAsync on the submit path: the configs[4]
-            // stalls were the submitter blocked ~8 ms inside those calls
-            // with the device idle (profiles/r3d_stall_trace.json)
-            s.t_h2d = steady_ns();
-            int rc = fn(e_, m, s.key, s.ts, s.n, s.cfg, nullptr, s.dec, s.rem, s.retry, s.reset, nullptr, os_);
-            if (rc == RL_OK && tally) rc = rl_tally_batch_device(e_, m, s.key, s.cfg, s.n, s.dec, os_);
-            if (rc == RL_OK && hot) rc = rl_hot_batch_device(e_, m, s.key, s.cfg, s.n, s.dec, os_);
-            if (rc != RL_OK) return rc;
-            return hipEventRecord(d.ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
+        const bool staged = m > zero_copy_max_;
+        Arrays a = s;   // the arrays the engine works on
+        if (staged) {
+            carve(d.key, M_, a);
+            bool ok = hipMemcpyAsync(a.key, s.key, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+            ok &= hipMemcpyAsync(a.ts, s.ts, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+            if (t.reads_n) ok &= hipMemcpyAsync(a.n, s.n, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+            ok &= hipMemcpyAsync(a.cfg, s.cfg, 4 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+            ok &= hipEventRecord(d.ev_in, cs_) == hipSuccess;
+            ok &= await_event(d.ev_in) == hipSuccess;
+            if (!ok) return RL_EDEVICE;
         }
-        bool ok = hipMemcpyAsync(dv.key, s.key, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipMemcpyAsync(dv.ts, s.ts, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipMemcpyAsync(dv.n, s.n, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipMemcpyAsync(dv.cfg, s.cfg, 4 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipEventRecord(d.ev_in, cs_) == hipSuccess;
-        ok &= await_event(d.ev_in) == hipSuccess;
-        if (!ok) return RL_EDEVICE;
         s.t_h2d = steady_ns();
-        int rc = fn(e_, m, dv.key, dv.ts, dv.n, dv.cfg, nullptr, dv.dec, dv.rem, dv.retry, dv.reset, nullptr, os_);
-        if (rc == RL_OK && tally) rc = rl_tally_batch_device(e_, m, dv.key, dv.cfg, dv.n, dv.dec, os_);
-        if (rc == RL_OK && hot) rc = rl_hot_batch_device(e_, m, dv.key, dv.cfg, dv.n, dv.dec, os_);
+        const int rc = engine_call(s.op, m, a);
         if (rc != RL_OK) return rc;
-        ok = hipMemcpyAsync(s.dec, dv.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
-        ok &= hipMemcpyAsync(s.rem, dv.rem, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
-        ok &= hipMemcpyAsync(s.retry, dv.retry, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
-        ok &= hipMemcpyAsync(s.reset, dv.reset, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
+        bool ok = true;
+        if (staged) {
+            ok = hipMemcpyAsync(s.dec, a.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
+            if (t.results) {
+                ok &= hipMemcpyAsync(s.rem, a.rem, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
+                ok &= hipMemcpyAsync(s.retry, a.retry, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
+                ok &= hipMemcpyAsync(s.reset, a.reset, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
+            }
+        }
         ok &= hipEventRecord(d.ev, os_) == hipSuccess;
         return ok ? RL_OK : RL_EDEVICE;
     }
-    int launch_reset_batch(int i, Slot& s) override {
-        (void)hipSetDevice(dev_id_);   // the submitter thread
-        Dev& d = dev_[i];
-        const size_t m = s.m;
-        // one kernel on the engine's replay stream between two batches; the
-        // output stream (and so this slot's completion event) waits for it
-        if (m <= zero_copy_max_) {
-            s.t_h2d = steady_ns();
-            const int rc = rl_reset_batch_device(e_, m, s.key, s.ts, s.cfg, s.dec, os_);
-            if (rc != RL_OK) return rc;
-            return hipEventRecord(d.ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
+    // The engine's work for one launch, enqueued so that os_ (and with it the
+    // slot's completion event) waits for it.  A reset or a refund is one or
+    // two kernels on the engine's replay stream between two batches.  Behind
+    // a successful decide, the tally and then the top keys count the batch on
+    // os_, on the arrays the decide used.
+    int engine_call(Op op, size_t m, const Arrays& a) {
+        switch (op) {
+            case OP_REQ: {
+                int rc = rl_decide_batch_device(e_, m, a.key, a.ts, a.n, a.cfg, nullptr, a.dec, a.rem, a.retry, a.reset,
+                                                nullptr, os_);
+                if (rc == RL_OK && tally_) rc = rl_tally_batch_device(e_, m, a.key, a.cfg, a.n, a.dec, os_);
+                if (rc == RL_OK && hot_) rc = rl_hot_batch_device(e_, m, a.key, a.cfg, a.n, a.dec, os_);
+                return rc;
+            }
+            case OP_PEEK:
+                return rl_peek_batch_device(e_, m, a.key, a.ts, a.n, a.cfg, nullptr, a.dec, a.rem, a.retry, a.reset, nullptr,
+                                            os_);
+            case OP_RESET: return rl_reset_batch_device(e_, m, a.key, a.ts, a.cfg, a.dec, os_);
+            case OP_REFUND: return rl_refund_batch_device(e_, m, a.key, a.ts, a.n, a.cfg, nullptr, a.dec, os_);
+            default: return RL_EINVAL;
         }
-        Slot dv;
-        carve(d.key, M_, dv);
-        bool ok = hipMemcpyAsync(dv.key, s.key, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipMemcpyAsync(dv.ts, s.ts, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipMemcpyAsync(dv.cfg, s.cfg, 4 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipEventRecord(d.ev_in, cs_) == hipSuccess;
-        ok &= await_event(d.ev_in) == hipSuccess;
-        if (!ok) return RL_EDEVICE;
-        s.t_h2d = steady_ns();
-        const int rc = rl_reset_batch_device(e_, m, dv.key, dv.ts, dv.cfg, dv.dec, os_);
-        if (rc != RL_OK) return rc;
-        ok = hipMemcpyAsync(s.dec, dv.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
-        ok &= hipEventRecord(d.ev, os_) == hipSuccess;
-        return ok ? RL_OK : RL_EDEVICE;
-    }
-    int launch_refund(int i, Slot& s) override {
-        (void)hipSetDevice(dev_id_);   // the submitter thread
-        Dev& d = dev_[i];
-        const size_t m = s.m;
-        // two kernels on the engine's replay stream between two batches; the
-        // output stream (and so this slot's completion event) waits for them
-        if (m <= zero_copy_max_) {
-            s.t_h2d = steady_ns();
-            const int rc = rl_refund_batch_device(e_, m, s.key, s.ts, s.n, s.cfg, nullptr, s.dec, os_);
-            if (rc != RL_OK) return rc;
-            return hipEventRecord(d.ev, os_) == hipSuccess ? RL_OK : RL_EDEVICE;
-        }
-        Slot dv;
-        carve(d.key, M_, dv);
-        bool ok = hipMemcpyAsync(dv.key, s.key, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipMemcpyAsync(dv.ts, s.ts, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipMemcpyAsync(dv.n, s.n, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipMemcpyAsync(dv.cfg, s.cfg, 4 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
-        ok &= hipEventRecord(d.ev_in, cs_) == hipSuccess;
-        ok &= await_event(d.ev_in) == hipSuccess;
-        if (!ok) return RL_EDEVICE;
-        s.t_h2d = steady_ns();
-        const int rc = rl_refund_batch_device(e_, m, dv.key, dv.ts, dv.n, dv.cfg, nullptr, dv.dec, os_);
-        if (rc != RL_OK) return rc;
-        ok = hipMemcpyAsync(s.dec, dv.dec, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
-        ok &= hipEventRecord(d.ev, os_) == hipSuccess;
-        return ok ? RL_OK : RL_EDEVICE;
     }
     int wait(int i, Slot&) override {
         (void)hipSetDevice(dev_id_);   // the completer thread
@@ -276,18 +229,6 @@ private:
         hipEvent_t ev = nullptr;       // results back on the host
         hipEvent_t ev_in = nullptr;    // inputs on the device
     };
-    // SoA layout of one slot block: key ts n | cfg | rem retry reset | dec
-    static void carve(uint8_t* p, size_t M, Slot& s) {
-        s.key = reinterpret_cast<uint64_t*>(p);
-        s.ts = reinterpret_cast<int64_t*>(p + 8 * M);
-        s.n = reinterpret_cast<int64_t*>(p + 16 * M);
-        s.cfg = reinterpret_cast<uint32_t*>(p + 24 * M);
-        uint8_t* q = p + ((28 * M + 63) & ~size_t(63));
-        s.rem = reinterpret_cast<int64_t*>(q);
-        s.retry = reinterpret_cast<int64_t*>(q + 8 * M);
-        s.reset = reinterpret_cast<int64_t*>(q + 16 * M);
-        s.dec = q + 24 * M;
-    }
     rl_engine* e_;
     bool tally_ = false;         // tally_enable succeeded: launch() counts its batches
     bool hot_ = false;           // hot_enable succeeded: the same for the top keys
@@ -303,21 +244,76 @@ private:
     size_t M_ = 0;
 };
 
+// What the usage tally and the top keys over a host backend share.
+//
+// A host backend registers no configs: a config id is known from the first
+// request of it the backend decided (any decision but RL_INVALID), up to
+// MAX_CFGS ids.
+struct KnownCfgs {
+    static constexpr uint32_t MAX_CFGS = 1u << 16;   // one request's config id sizes the tally's rows: 3 MiB at most
+    uint32_t n = 0;
+    // request (config c, decision d) is of a known config (which it may make known)
+    bool admit(uint32_t c, uint32_t d) {
+        if (c >= n) {
+            if (d >= RL_INVALID || c >= MAX_CFGS) return false;
+            n = c + 1;
+        }
+        return true;
+    }
+};
+
+// The key table of csrc/rl_tally.h and csrc/rl_hot.h in plain C++: rows with a
+// key_id and a cfg_id, home slot mix64(key) & mask, linear probing over
+// min(slots, 64) slots, a slot never released before a clear.
+template <class Row>
+struct KeyTable {
+    static constexpr uint64_t PROBES = 64;
+    std::vector<Row> rows;
+    void assign(uint64_t slots) {   // all free: enable, and clear
+        Row free{};
+        free.key_id = RL_KEY_RESERVED;
+        rows.assign(slots, free);
+    }
+    // the key's row, claimed on the way (and counted in *tracked) when it had
+    // none; null: no room within the probes
+    Row* find_or_claim(uint64_t k, uint32_t c, uint64_t* tracked) {
+        const uint64_t mask = rows.size() - 1, probes = std::min<uint64_t>(rows.size(), PROBES);
+        uint64_t s = rl::mix64(k) & mask;
+        for (uint64_t p = 0; p < probes; p++, s = (s + 1) & mask) {
+            Row& r = rows[s];
+            if (r.key_id == RL_KEY_RESERVED) {
+                r.key_id = k;
+                r.cfg_id = c;
+                (*tracked)++;
+            }
+            if (r.key_id == k) return &r;
+        }
+        return nullptr;
+    }
+    // the `cap` rows in use with the largest `by` (ties: the smaller key id
+    // first), in that order
+    void top(Row* out, size_t cap, uint64_t Row::*by) const {
+        if (!out || !cap) return;
+        std::vector<Row> tab;
+        for (const Row& r : rows)
+            if (r.key_id != RL_KEY_RESERVED) tab.push_back(r);
+        const size_t want = std::min(cap, tab.size());
+        std::partial_sort(tab.begin(), tab.begin() + want, tab.end(), [by](const Row& x, const Row& y) {
+            return x.*by != y.*by ? x.*by > y.*by : x.key_id < y.key_id;
+        });
+        memcpy(out, tab.data(), sizeof(Row) * want);
+    }
+};
+
 // The usage tally over a host backend: k_tally's sums (csrc/rl_tally.h) one
-// request at a time -- the same per-config counters, the same key table (home
-// slot mix64(key) & mask, linear probing over min(slots, 64) slots, a slot
-// never released before a clear).  A host backend registers no configs: a
-// config id is known from the first request of it the backend decided (any
-// decision but RL_INVALID), up to MAX_ROWS ids.
+// request at a time -- the same per-config counters, the same key table.
 class HostTally {
 public:
-    static constexpr uint64_t PROBES = 64;
-    static constexpr uint32_t MAX_ROWS = 1u << 16;   // one request's config id sizes the rows: 3 MiB at most
     int enable(uint32_t key_slots) {
         if (key_slots > (1u << 24)) return RL_EINVAL;
         uint64_t slots = 16;
         while (slots < (key_slots ? key_slots : 65536u)) slots *= 2;
-        keys_.assign(slots, free_key());
+        keys_.assign(slots);
         return RL_OK;
     }
     void add(size_t m, const uint64_t* key, const uint32_t* cfg, const int64_t* n, const uint8_t* dec) {
@@ -325,10 +321,8 @@ public:
         info_.requests += m;
         for (size_t i = 0; i < m; i++) {
             const uint32_t c = cfg[i], d = dec[i];
-            if (c >= rows_.size()) {
-                if (d >= RL_INVALID || c >= MAX_ROWS) { info_.unknown_cfg++; continue; }
-                rows_.resize((size_t)c + 1, rl_tally_cfg{});
-            }
+            if (!known_.admit(c, d)) { info_.unknown_cfg++; continue; }
+            if (known_.n > rows_.size()) rows_.resize(known_.n, rl_tally_cfg{});
             if (d > 3) { info_.bad_codes++; continue; }
             const uint64_t u = n[i] > 0 ? (uint64_t)n[i] : 0;
             rows_[c].count[d]++;
@@ -340,61 +334,37 @@ public:
         const size_t rows = a.cfg_out ? std::min(a.cfg_cap, rows_.size()) : 0;
         if (rows) memcpy(a.cfg_out, rows_.data(), sizeof(rl_tally_cfg) * rows);
         if (a.ncfg) *a.ncfg = (uint32_t)rows_.size();
-        if (a.key_out && a.key_cap) {
-            std::vector<rl_tally_key> tab;
-            for (const auto& r : keys_)
-                if (r.key_id != RL_KEY_RESERVED) tab.push_back(r);
-            const size_t want = std::min(a.key_cap, tab.size());
-            std::partial_sort(tab.begin(), tab.begin() + want, tab.end(), [](const rl_tally_key& x, const rl_tally_key& y) {
-                return x.denied != y.denied ? x.denied > y.denied : x.key_id < y.key_id;
-            });
-            memcpy(a.key_out, tab.data(), sizeof(rl_tally_key) * want);
-        }
+        keys_.top(a.key_out, a.key_cap, &rl_tally_key::denied);
         if (a.keys_tracked) *a.keys_tracked = info_.keys_tracked;
         if (a.info) {
             if (a.info->struct_size < 8) return RL_EINVAL;
             rl_tally_info I = info_;
-            I.key_slots = keys_.size();
-            I.struct_size = (uint32_t)std::min<size_t>(a.info->struct_size, sizeof I);   // bytes filled in
-            memcpy(a.info, &I, I.struct_size);
+            I.key_slots = keys_.rows.size();
+            copy_out_sized(a.info, I);
         }
         if (a.clear) {
             // the config ids seen stay known: their rows are zero
             std::fill(rows_.begin(), rows_.end(), rl_tally_cfg{});
-            std::fill(keys_.begin(), keys_.end(), free_key());
+            keys_.assign(keys_.rows.size());
             info_ = rl_tally_info{};
         }
         return RL_OK;
     }
 
 private:
-    static rl_tally_key free_key() { return rl_tally_key{RL_KEY_RESERVED, 0, 0, 0, 0}; }
-    static uint64_t mix64(uint64_t x) {   // csrc/rl_table.h
-        x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL;
-        x ^= x >> 27; x *= 0x94d049bb133111ebULL;
-        x ^= x >> 31; return x;
-    }
     void denied(uint64_t k, uint32_t c, uint64_t u) {
-        const uint64_t mask = keys_.size() - 1, probes = std::min<uint64_t>(keys_.size(), PROBES);
-        uint64_t s = mix64(k) & mask;
-        for (uint64_t p = 0; p < probes && k != RL_KEY_RESERVED; p++, s = (s + 1) & mask) {
-            rl_tally_key& r = keys_[s];
-            if (r.key_id == RL_KEY_RESERVED) {
-                r.key_id = k;
-                r.cfg_id = c;
-                info_.keys_tracked++;
-            }
-            if (r.key_id == k) {
-                r.denied++;
-                r.units_denied += u;
-                return;
-            }
+        rl_tally_key* r = k != RL_KEY_RESERVED ? keys_.find_or_claim(k, c, &info_.keys_tracked) : nullptr;
+        if (r) {
+            r->denied++;
+            r->units_denied += u;
+        } else {
+            info_.untracked_requests++;
+            info_.untracked_units += u;
         }
-        info_.untracked_requests++;
-        info_.untracked_units += u;
     }
+    KnownCfgs known_;
     std::vector<rl_tally_cfg> rows_;
-    std::vector<rl_tally_key> keys_;
+    KeyTable<rl_tally_key> keys_;
     rl_tally_info info_{};
 };
 
@@ -402,13 +372,9 @@ private:
 // csrc/rl_hot.h in plain C++ -- per backend batch every counted request's adds
 // (A), then the look at the batch's keys (B): estimate = the minimum of the
 // key's four counters; at or above hot_min the key is looked up in the table
-// (home slot mix64(key) & mask, linear probing over min(slots, 64) slots, never
-// released before a clear) and inserted when absent.  A config id counts as
-// known by HostTally's rule: from the first request of it the backend decided
-// (any decision but RL_INVALID), up to HostTally::MAX_ROWS ids.
+// and inserted when absent.
 class HostHot {
 public:
-    static constexpr uint64_t PROBES = 64;
     int enable(const rl_hot_opts& o) {
         if (o.struct_size != sizeof(rl_hot_opts) || o.width > (1u << 24) || o.key_slots > (1u << 24) ||
             o.weight > RL_HOT_UNITS || o.hot_min < 1)
@@ -420,8 +386,8 @@ public:
         units_ = o.weight == RL_HOT_UNITS;
         hot_min_ = o.hot_min;
         sketch_.assign(RL_HOT_DEPTH * width, 0);
-        keys_.assign(slots, free_key());
-        for (int r = 0; r < RL_HOT_DEPTH; r++) salt_[r] = mix64((uint64_t)r + 1);
+        keys_.assign(slots);
+        for (int r = 0; r < RL_HOT_DEPTH; r++) salt_[r] = rl::mix64((uint64_t)r + 1);
         return RL_OK;
     }
     void add(size_t m, const uint64_t* key, const uint32_t* cfg, const int64_t* n, const uint8_t* dec) {
@@ -430,29 +396,25 @@ public:
         counted_.assign(m, 0);
         for (size_t i = 0; i < m; i++) {                         // (A)
             const uint32_t c = cfg[i], d = dec[i];
-            if (c >= ncfg_) {
-                if (d >= RL_INVALID || c >= HostTally::MAX_ROWS) { info_.skipped++; continue; }
-                ncfg_ = c + 1;
+            if (!known_.admit(c, d) || d > RL_ERROR || key[i] == RL_KEY_RESERVED || (units_ && n[i] <= 0)) {
+                info_.skipped++;
+                continue;
             }
-            if (d > RL_ERROR || key[i] == RL_KEY_RESERVED || (units_ && n[i] <= 0)) { info_.skipped++; continue; }
             const uint64_t w = units_ ? (uint64_t)n[i] : 1;
             counted_[i] = 1;
             info_.total += w;
             for (int r = 0; r < RL_HOT_DEPTH; r++) sketch_[r * width_ + col(key[i], r)] += w;
         }
         for (size_t i = 0; i < m; i++)                            // (B)
-            if (counted_[i] && estimate(key[i]) >= hot_min_) claim(key[i], cfg[i]);
+            if (counted_[i] && estimate(key[i]) >= hot_min_ && !keys_.find_or_claim(key[i], cfg[i], &info_.keys_tracked))
+                info_.dropped = 1;
     }
     int read(const HotArgs& a) {
         if (a.key_out && a.key_cap) {
-            std::vector<rl_hot_key> tab;
-            for (const auto& r : keys_)
-                if (r.key_id != RL_KEY_RESERVED) tab.push_back(rl_hot_key{r.key_id, estimate(r.key_id), r.cfg_id, 0});
-            const size_t want = std::min(a.key_cap, tab.size());
-            std::partial_sort(tab.begin(), tab.begin() + want, tab.end(), [](const rl_hot_key& x, const rl_hot_key& y) {
-                return x.estimate != y.estimate ? x.estimate > y.estimate : x.key_id < y.key_id;
-            });
-            memcpy(a.key_out, tab.data(), sizeof(rl_hot_key) * want);
+            // a row's estimate is looked up when it is read (a free row's stays 0)
+            for (rl_hot_key& r : keys_.rows)
+                if (r.key_id != RL_KEY_RESERVED) r.estimate = estimate(r.key_id);
+            keys_.top(a.key_out, a.key_cap, &rl_hot_key::estimate);
         }
         if (a.keys_tracked) *a.keys_tracked = info_.keys_tracked;
         if (a.info) {
@@ -460,54 +422,33 @@ public:
             rl_hot_info I = info_;
             I.width = width_;
             I.depth = RL_HOT_DEPTH;
-            I.key_slots = keys_.size();
+            I.key_slots = keys_.rows.size();
             I.hot_min = hot_min_;
             I.weight = units_ ? RL_HOT_UNITS : RL_HOT_REQUESTS;
-            I.struct_size = (uint32_t)std::min<size_t>(a.info->struct_size, sizeof I);   // bytes filled in
-            memcpy(a.info, &I, I.struct_size);
+            copy_out_sized(a.info, I);
         }
         if (a.clear) {
             // the config ids seen stay known
             std::fill(sketch_.begin(), sketch_.end(), 0);
-            std::fill(keys_.begin(), keys_.end(), free_key());
+            keys_.assign(keys_.rows.size());
             info_ = rl_hot_info{};
         }
         return RL_OK;
     }
 
 private:
-    static rl_hot_key free_key() { return rl_hot_key{RL_KEY_RESERVED, 0, 0, 0}; }
-    static uint64_t mix64(uint64_t x) {   // csrc/rl_table.h
-        x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL;
-        x ^= x >> 27; x *= 0x94d049bb133111ebULL;
-        x ^= x >> 31; return x;
-    }
-    uint64_t col(uint64_t k, int r) const { return mix64(k ^ salt_[r]) & (width_ - 1); }
+    uint64_t col(uint64_t k, int r) const { return rl::mix64(k ^ salt_[r]) & (width_ - 1); }
     uint64_t estimate(uint64_t k) const {
         uint64_t est = ~0ull;
         for (int r = 0; r < RL_HOT_DEPTH; r++) est = std::min(est, sketch_[r * width_ + col(k, r)]);
         return est;
     }
-    void claim(uint64_t k, uint32_t c) {
-        const uint64_t mask = keys_.size() - 1, probes = std::min<uint64_t>(keys_.size(), PROBES);
-        uint64_t s = mix64(k) & mask;
-        for (uint64_t p = 0; p < probes; p++, s = (s + 1) & mask) {
-            rl_hot_key& r = keys_[s];
-            if (r.key_id == RL_KEY_RESERVED) {
-                r.key_id = k;
-                r.cfg_id = c;
-                info_.keys_tracked++;
-            }
-            if (r.key_id == k) return;
-        }
-        info_.dropped = 1;
-    }
+    KnownCfgs known_;
     std::vector<uint64_t> sketch_;
-    std::vector<rl_hot_key> keys_;
+    KeyTable<rl_hot_key> keys_;
     std::vector<uint8_t> counted_;
     uint64_t salt_[RL_HOT_DEPTH] = {};
     uint64_t width_ = 0, hot_min_ = 0;
-    uint32_t ncfg_ = 0;
     bool units_ = false;
     rl_hot_info info_{};
 };
@@ -532,30 +473,38 @@ public:
         slots->resize(nslots);
         mem_.resize(nslots);
         for (int i = 0; i < nslots; i++) {
-            mem_[i].reset(new uint8_t[M * 61 + 64]);
-            uint8_t* p = mem_[i].get();
-            Slot& s = (*slots)[i];
-            s.key = reinterpret_cast<uint64_t*>(p);
-            s.ts = reinterpret_cast<int64_t*>(p + 8 * M);
-            s.n = reinterpret_cast<int64_t*>(p + 16 * M);
-            s.rem = reinterpret_cast<int64_t*>(p + 24 * M);
-            s.retry = reinterpret_cast<int64_t*>(p + 32 * M);
-            s.reset = reinterpret_cast<int64_t*>(p + 40 * M);
-            s.cfg = reinterpret_cast<uint32_t*>(p + 48 * M);
-            s.dec = p + 52 * M;
+            mem_[i].reset(new uint8_t[block_bytes(M)]);
+            carve(mem_[i].get(), M, (*slots)[i]);
         }
         return RL_OK;
     }
     int launch(int, Slot& s) override {
         s.t_h2d = steady_ns();
-        const int rc = b_.batch(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset);
-        // launch() and tally_read() both run on the submitter thread
-        if (rc == RL_OK && tally_on_) tally_.add(s.m, s.key, s.cfg, s.n, s.dec);
-        if (rc == RL_OK && hot_on_) hot_.add(s.m, s.key, s.cfg, s.n, s.dec);
-        return rc;
+        switch (s.op) {
+            case OP_REQ: {
+                const int rc = b_.batch(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset);
+                // launch() and tally_read() both run on the submitter thread
+                if (rc == RL_OK && tally_on_) tally_.add(s.m, s.key, s.cfg, s.n, s.dec);
+                if (rc == RL_OK && hot_on_) hot_.add(s.m, s.key, s.cfg, s.n, s.dec);
+                return rc;
+            }
+            case OP_PEEK:
+                return b_.peek ? b_.peek(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset) : RL_EINVAL;
+            case OP_REFUND: return b_.refund ? b_.refund(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec) : RL_EINVAL;
+            case OP_RESET: return reset_batch(s);
+            default: return RL_EINVAL;
+        }
     }
-    int launch_reset_batch(int, Slot& s) override {
-        s.t_h2d = steady_ns();
+    int wait(int, Slot&) override { return RL_OK; }
+    int table_info(int64_t now_ms, rl_table_info* out) override {
+        return b_.table_info ? b_.table_info(b_.user, now_ms, out) : RL_EINVAL;
+    }
+    int gc(int64_t now_ms, uint64_t tb_cap, uint64_t win_cap, rl_table_info* out) override {
+        return b_.gc ? b_.gc(b_.user, now_ms, tb_cap, win_cap, out) : RL_EINVAL;
+    }
+
+private:
+    int reset_batch(Slot& s) {
         if (b_.reset_batch) return b_.reset_batch(b_.user, s.m, s.key, s.ts, s.cfg, s.dec);
         if (!b_.reset) return RL_EINVAL;
         // a backend without reset_batch: one reset call per key, in order; its
@@ -567,23 +516,6 @@ public:
         }
         return RL_OK;
     }
-    int launch_peek(int, Slot& s) override {
-        s.t_h2d = steady_ns();
-        return b_.peek ? b_.peek(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset) : RL_EINVAL;
-    }
-    int launch_refund(int, Slot& s) override {
-        s.t_h2d = steady_ns();
-        return b_.refund ? b_.refund(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec) : RL_EINVAL;
-    }
-    int wait(int, Slot&) override { return RL_OK; }
-    int table_info(int64_t now_ms, rl_table_info* out) override {
-        return b_.table_info ? b_.table_info(b_.user, now_ms, out) : RL_EINVAL;
-    }
-    int gc(int64_t now_ms, uint64_t tb_cap, uint64_t win_cap, rl_table_info* out) override {
-        return b_.gc ? b_.gc(b_.user, now_ms, tb_cap, win_cap, out) : RL_EINVAL;
-    }
-
-private:
     rl_coalescer_backend b_;
     HostTally tally_;
     bool tally_on_ = false;
@@ -667,10 +599,11 @@ void Coalescer::SetNotify(NotifyFn fn, void* user) {
 
 int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
                       uint64_t* ticket, int64_t deadline, void* tag, Op op) {
-    if (!ticket || (m && (!key || !ts || !cfg || (!n && op != OP_RESET))) || deadline < 0 || !is_batched(op))
-        return RL_EINVAL;
-    // a refund submission is one launch: never split (the engine's sum rule)
-    if (op == OP_REFUND && m > o_.max_batch) return RL_EINVAL;
+    if (op >= OP_COUNT || !OPS[op].batched) return RL_EINVAL;
+    const OpTraits& t = OPS[op];
+    if (!ticket || (m && (!key || !ts || !cfg || (!n && t.reads_n))) || deadline < 0) return RL_EINVAL;
+    // a submission that is not split is one launch (a refund: the engine's sum rule)
+    if (!t.splits && m > o_.max_batch) return RL_EINVAL;
     Sub* s = get_sub(m);
     s->op = op;
     s->deadline = deadline;
@@ -680,10 +613,23 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
     memcpy(s->ts, ts, 8 * m);
     if (n) memcpy(s->n, n, 8 * m);
     memcpy(s->cfg, cfg, 4 * m);
+    return enqueue(s, m, ticket);
+}
+
+int Coalescer::SubmitOp(Op op, const OpArgs& a, uint64_t* ticket, void* tag) {
+    if (op >= OP_COUNT || OPS[op].batched || !ticket) return RL_EINVAL;
+    Sub* s = get_sub(1);
+    s->op = op;
+    s->tag = tag;
+    s->args = a;
+    if (trace_cap_) s->submit_ns = steady_ns();
+    return enqueue(s, 1, ticket);
+}
+
+int Coalescer::enqueue(Sub* s, size_t m, uint64_t* ticket) {
     {
         std::lock_guard<std::mutex> g(mu_);
-        // a Reset is never turned away by a full queue
-        if (stop_ || (pending_ + m > o_.queue_cap && op != OP_RESET)) {
+        if (stop_ || (pending_ + m > o_.queue_cap && OPS[s->op].queue_cap)) {
             const int rc = stop_ ? RL_ECLOSED : RL_EAGAIN;
             put_sub(s);
             return rc;
@@ -692,15 +638,13 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
         // an empty submission is done at once; its ticket must still be unique
         next_seq_ += m ? m : 1;
         subs_[s->first] = s;
-        if (op == OP_REQ) st_.submitted += m;
+        if (OPS[s->op].decides) st_.submitted += m;
         if (m) {
             queue_.push_back(s);
             s->in_queue = true;
             pending_ += m;
         } else {
-            s->done = true;
-            s->done_ns = steady_ns();
-            notify_locked(s);
+            finish_locked(s, steady_ns());
         }
         *ticket = s->first;
         // wake the submitter only when it sleeps: at millions of submissions
@@ -711,76 +655,23 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
     return RL_OK;
 }
 
-int Coalescer::SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
-                        uint64_t cap_win, uint64_t* ticket, void* tag, const SnapArgs* snap, const TallyArgs* tally,
-                        const HotArgs* hot) {
-    Sub* s = get_sub(1);
-    s->op = op;
-    s->tag = tag;
-    if (snap) s->snap = *snap;
-    if (tally) s->tally = *tally;
-    if (hot) s->hot = *hot;
-    s->key[0] = key;
-    s->ts[0] = ts;
-    s->n[0] = 1;
-    s->cfg[0] = cfg;
-    s->now_ms = now_ms;
-    s->cap_tb = cap_tb;
-    s->cap_win = cap_win;
-    if (trace_cap_) s->submit_ns = steady_ns();
-    {
-        std::lock_guard<std::mutex> g(mu_);
-        if (stop_) {
-            put_sub(s);
-            return RL_ECLOSED;
-        }
-        s->first = next_seq_++;
-        subs_[s->first] = s;
-        queue_.push_back(s);
-        s->in_queue = true;
-        pending_ += 1;
-        *ticket = s->first;
-        if (!sub_idle_) return RL_OK;
-    }
-    cv_sub_.notify_one();
-    return RL_OK;
-}
-
-void Coalescer::drop_locked(Sub* s, int code) {
-    // none of it was launched: every request is still pending
-    pending_ -= s->m - s->taken;
-    if (s->op == OP_REQ) (code == RL_ECANCELED ? st_.cancelled : st_.expired) += s->m;
-    s->dropped = true;
-    s->done = true;
-    s->status = code;
-    s->left = 0;
-    s->done_ns = steady_ns();
-    if (s->waiting) s->cv.notify_all();
-    notify_locked(s);
-}
-
-void Coalescer::truncate_locked(Sub* s, int code) {
-    // part of it was launched (applied, as an EVAL already sent); the part not
-    // yet launched is dropped unapplied, so nothing is sent after its context
-    // ended.  taken = m stops the submitter; it pops the submission when it
-    // reaches the head of the queue
+void Coalescer::end_unlaunched_locked(Sub* s, int code) {
     const size_t rest = s->m - s->taken;
     if (rest == 0) return;
-    // the outcome is the context's error, whoever completes it: the results
-    // of the launched part are discarded and the tail never ran (its result
-    // arrays hold whatever a pooled Sub held before)
-    s->truncated = true;
-    s->status = code;
     pending_ -= rest;
-    if (s->op == OP_REQ) (code == RL_ECANCELED ? st_.cancelled : st_.expired) += rest;
-    s->taken = s->m;
-    s->left -= rest;
-    if (s->left == 0 && !s->done) {
-        s->done = true;
-        s->done_ns = steady_ns();
-        if (s->waiting) s->cv.notify_all();
-        notify_locked(s);
+    if (OPS[s->op].decides) (code == RL_ECANCELED ? st_.cancelled : st_.expired) += rest;
+    // the outcome is the context's error, whoever completes it: the results
+    // of a launched part are discarded and the rest never ran (its result
+    // arrays hold whatever a pooled Sub held before)
+    s->status = code;
+    if (s->taken == 0) {
+        s->dropped = true;
+    } else {
+        s->truncated = true;
+        s->taken = s->m;
     }
+    s->left -= rest;
+    if (s->left == 0 && !s->done) finish_locked(s, steady_ns());
 }
 
 void Coalescer::maybe_free_locked(Sub* s) {
@@ -794,11 +685,8 @@ int Coalescer::Cancel(uint64_t ticket) {
     Sub* s = it->second;
     if (s->done) return RL_OK;
     s->cancelled = true;
-    if (s->taken == 0) drop_locked(s, RL_ECANCELED);
-    else {
-        truncate_locked(s, RL_ECANCELED);
-        if (s->waiting) s->cv.notify_all();
-    }
+    end_unlaunched_locked(s, RL_ECANCELED);
+    if (s->waiting) s->cv.notify_all();   // a waiter whose launched part is still out sees `cancelled`
     return RL_OK;
 }
 
@@ -820,8 +708,7 @@ int Coalescer::Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* 
         if (s->deadline && now >= s->deadline) {
             // not launched: never applied; launched: applied, results discarded,
             // and what was not launched yet never will be
-            if (s->taken == 0) drop_locked(s, RL_EDEADLINE);
-            else truncate_locked(s, RL_EDEADLINE);
+            end_unlaunched_locked(s, RL_EDEADLINE);
             code = RL_EDEADLINE;
             break;
         }
@@ -845,10 +732,10 @@ int Coalescer::Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* 
     // done and applied: no slot or queue references it any more
     lk.unlock();
     const size_t m = s->m;
-    if (s->op == OP_RESET || s->op == OP_REFUND) {
-        if (dec) memcpy(dec, s->dec, m);   // the per-request status
-    } else if (has_requests(s->op)) {
-        if (dec) memcpy(dec, s->dec, m);
+    if (OPS[s->op].batched) {
+        if (dec) memcpy(dec, s->dec, m);   // the decision, or the per-request status
+    }
+    if (OPS[s->op].results) {
         if (rem) memcpy(rem, s->rem, 8 * m);
         if (retry) memcpy(retry, s->retry, 8 * m);
         if (reset) memcpy(reset, s->reset, 8 * m);
@@ -868,7 +755,7 @@ Sub* Coalescer::get_sub(size_t m) {
             if (s->cap >= m && s->cap <= 4 * m + 4096) {   // fits, and not far too big
                 pool_[i] = pool_.back();
                 pool_.pop_back();
-                s->carve(m);
+                s->renew(m);
                 return s;
             }
         }
@@ -905,26 +792,25 @@ rl_coalescer_stats Coalescer::Stats() {
 }
 
 int Coalescer::run_table_op(Sub* op) {
+    const OpArgs& a = op->args;
     rl_table_info info{};
     info.struct_size = sizeof info;
     int st;
-    if (op->op == OP_INFO) {
-        st = be_->table_info(op->now_ms, &info);
-    } else if (op->op == OP_TALLY) {
+    switch (op->op) {
+        case OP_INFO: st = be_->table_info(a.now_ms, &info); break;
         // every batch before it is launched, its tally enqueued behind it
-        st = be_->tally_read(op->tally);
-    } else if (op->op == OP_HOT) {
-        st = be_->hot_read(op->hot);
-    } else if (op->op == OP_SNAPSHOT) {
-        st = be_->snapshot(op->now_ms, op->snap.world, op->snap.rank, op->snap.buf, op->snap.len, op->snap.out);
-    } else {
-        // a restore is a GC that also merges a snapshot
-        st = op->op == OP_RESTORE
-                 ? be_->restore(op->snap.buf, op->snap.len, op->now_ms, op->cap_tb, op->cap_win, &info)
-                 : be_->gc(op->now_ms, op->cap_tb, op->cap_win, &info);
-        std::lock_guard<std::mutex> g(mu_);
-        st_.gc_runs++;
-        if (st != RL_OK) st_.gc_failures++;
+        case OP_TALLY: st = be_->tally_read(a.tally); break;
+        case OP_HOT: st = be_->hot_read(a.hot); break;
+        case OP_SNAPSHOT:
+            st = be_->snapshot(a.now_ms, a.snap.world, a.snap.rank, a.snap.buf, a.snap.len, a.snap.out);
+            break;
+        default: {   // OP_GC, OP_RESTORE: a restore is a GC that also merges a snapshot
+            st = op->op == OP_RESTORE ? be_->restore(a.snap.buf, a.snap.len, a.now_ms, a.cap_tb, a.cap_win, &info)
+                                      : be_->gc(a.now_ms, a.cap_tb, a.cap_win, &info);
+            std::lock_guard<std::mutex> g(mu_);
+            st_.gc_runs++;
+            if (st != RL_OK) st_.gc_failures++;
+        }
     }
     op->info = info;
     return st;
@@ -1021,15 +907,10 @@ void Coalescer::submitter() {
         if (pending_ == 0) break;   // stop_ with nothing left
         // submissions dropped while queued (deadline, cancel) leave the queue here
         auto pop_dropped = [&] {
-            while (!queue_.empty() && queue_.front()->dropped) {
-                Sub* d = queue_.front();
-                queue_.pop_front();
-                d->in_queue = false;
-                maybe_free_locked(d);
-            }
+            while (!queue_.empty() && queue_.front()->dropped) maybe_free_locked(pop_front_locked());
         };
         pop_dropped();
-        if (o_.linger_ns > 0 && inflight_ == 0 && pending_ < o_.max_batch && !stop_ && queue_.front()->op == OP_REQ) {
+        if (o_.linger_ns > 0 && inflight_ == 0 && pending_ < o_.max_batch && !stop_ && OPS[queue_.front()->op].decides) {
             const auto until = std::chrono::steady_clock::now() + std::chrono::nanoseconds(o_.linger_ns);
             sub_idle_ = true;
             cv_sub_.wait_until(lk, until, [&] { return stop_ || pending_ >= o_.max_batch; });
@@ -1038,60 +919,49 @@ void Coalescer::submitter() {
             if (pending_ == 0) continue;
         }
         Sub* f = queue_.front();
-        if (is_table_op(f->op)) {
-            // synchronous, on this thread: every batch before it is launched
-            // and the backend drains them; nothing after it is launched yet
-            queue_.pop_front();
-            f->in_queue = false;
+        const OpTraits& t = OPS[f->op];
+        if (!t.batched) {
+            // a table operation: synchronous, on this thread: every batch
+            // before it is launched and the backend drains them; nothing after
+            // it is launched yet
+            pop_front_locked();
             pending_ -= 1;
             f->taken = 1;
-            const Op fop = f->op;
             lk.unlock();
             const int st = run_table_op(f);
             lk.lock();
             f->status = st;
             f->left = 0;
-            f->done = true;
-            f->done_ns = steady_ns();
-            if (f->waiting) f->cv.notify_all();
-            notify_locked(f);
+            finish_locked(f, steady_ns());
             maybe_free_locked(f);
-            // a manual GC invalidates the automatic GC's count (a tally or top-keys read touches no table)
-            if (fop != OP_TALLY && fop != OP_HOT) gc_counted_ = false;
+            // a manual GC invalidates the automatic GC's count
+            if (!t.keeps_gc_count) gc_counted_ = false;
             continue;
         }
         const int si = next_slot_;
         Slot& s = slots_[si];
         s.parts.clear();
-        // resets: the run of adjacent reset submissions at the queue head is
-        // one launch, enqueued between the batches around it
-        s.is_reset = f->op == OP_RESET;
-        s.is_peek = f->op == OP_PEEK;
-        s.is_refund = f->op == OP_REFUND;
+        s.op = f->op;
         size_t m = 0;
         const int64_t now = steady_ns();
         while (m < o_.max_batch && !queue_.empty()) {
             Sub* sub = queue_.front();
             if (sub->dropped) {
-                queue_.pop_front();
-                sub->in_queue = false;
-                maybe_free_locked(sub);
+                maybe_free_locked(pop_front_locked());
                 continue;
             }
-            // requests merge, and so do resets; a peek submission is launched
-            // on its own, and so is a refund submission (one engine call: the
-            // engine sums the refunds of a call per target)
-            if (sub->op != f->op || ((s.is_peek || s.is_refund) && sub != f)) break;
-            if (sub->taken < sub->m && (sub->cancelled || (sub->deadline && sub->deadline <= now))) {
-                // its context ended before (the rest of) it was sent: that part is never applied
-                if (sub->taken == 0) drop_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
-                else truncate_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
-            }
+            // requests merge, and so do resets: the run of adjacent ones at
+            // the queue head is one launch, enqueued between the batches
+            // around it; a peek submission is launched on its own, and so is
+            // a refund submission (one engine call: the engine sums the
+            // refunds of a call per target)
+            if (sub->op != f->op || (!t.merges && sub != f)) break;
+            // its context ended before (the rest of) it was sent: that part is never applied
+            if (sub->taken < sub->m && (sub->cancelled || (sub->deadline && sub->deadline <= now)))
+                end_unlaunched_locked(sub, sub->cancelled ? RL_ECANCELED : RL_EDEADLINE);
             if (sub->dropped || sub->taken == sub->m) {
                 // dropped, or the rest of a split submission truncated: nothing left to launch
-                queue_.pop_front();
-                sub->in_queue = false;
-                maybe_free_locked(sub);
+                maybe_free_locked(pop_front_locked());
                 continue;
             }
             const size_t take = std::min(sub->m - sub->taken, (size_t)o_.max_batch - m);
@@ -1099,10 +969,7 @@ void Coalescer::submitter() {
             sub->taken += take;
             sub->inflight++;
             m += take;
-            if (sub->taken == sub->m) {
-                queue_.pop_front();
-                sub->in_queue = false;
-            }
+            if (sub->taken == sub->m) pop_front_locked();
         }
         if (m == 0) continue;   // everything at the head was dropped
         pending_ -= m;
@@ -1114,46 +981,25 @@ void Coalescer::submitter() {
         for (const auto& p : s.parts) {
             memcpy(s.key + p.at, p.sub->key + p.off, 8 * p.count);
             memcpy(s.ts + p.at, p.sub->ts + p.off, 8 * p.count);
-            if (!s.is_reset) memcpy(s.n + p.at, p.sub->n + p.off, 8 * p.count);
+            if (t.reads_n) memcpy(s.n + p.at, p.sub->n + p.off, 8 * p.count);
             memcpy(s.cfg + p.at, p.sub->cfg + p.off, 4 * p.count);
         }
         s.m = m;
-        if (s.is_reset) {
-            // inserts nothing: no part in the automatic GC's budgets
-            s.status = be_->launch_reset_batch(si, s);
-        } else if (s.is_peek) {
-            // inserts nothing: no part in the automatic GC's budgets
-            s.status = be_->launch_peek(si, s);
-        } else if (s.is_refund) {
-            // inserts nothing either
-            s.status = be_->launch_refund(si, s);
-        } else {
-            auto_gc(s);
-            s.status = be_->launch(si, s);
-        }
+        // only a decision inserts: the others have no part in the automatic GC's budgets
+        if (t.decides) auto_gc(s);
+        s.status = be_->launch(si, s);
         if (trace_cap_) s.t_launched = steady_ns();
         lk.lock();
-        if (s.is_reset) {
-            st_.batches++;          // a launch, but no request batch: max_batch_seen stays
-            st_.reset_launches++;
-        } else if (s.is_refund) {
-            st_.refund_launches++;
-        } else if (!s.is_peek) {
-            st_.batches++;
-            st_.max_batch_seen = std::max<uint64_t>(st_.max_batch_seen, m);
-        }
+        if (t.counts_batch) st_.batches++;   // a reset launch too, though it is no request batch: max_batch_seen stays
+        if (t.counts_max) st_.max_batch_seen = std::max<uint64_t>(st_.max_batch_seen, m);
+        if (t.launches) (st_.*t.launches)++;
         launched_.push_back(si);
         lk.unlock();
         cv_done_.notify_one();
     }
     std::lock_guard<std::mutex> g(mu_);
     // only dropped submissions can be left in the queue
-    while (!queue_.empty()) {
-        Sub* d = queue_.front();
-        queue_.pop_front();
-        d->in_queue = false;
-        maybe_free_locked(d);
-    }
+    while (!queue_.empty()) maybe_free_locked(pop_front_locked());
     sub_exited_ = true;
     cv_done_.notify_all();
 }
@@ -1168,21 +1014,24 @@ void Coalescer::completer() {
             si = launched_.front();
         }
         Slot& s = slots_[si];
+        const OpTraits& t = OPS[s.op];
         const int64_t t_wait = trace_cap_ ? steady_ns() : 0;
         int st = s.status == RL_OK ? be_->wait(si, s) : s.status;
-        uint64_t nreset = 0;
-        if (s.is_reset || s.is_refund) {
-            // RL_RESET_DONE and RL_REFUND_DONE are the same code
-            if (st == RL_OK) {
-                for (const auto& p : s.parts) memcpy(p.sub->dec + p.off, s.dec + p.at, p.count);
-                for (size_t i = 0; i < s.m; i++) nreset += s.dec[i] == RL_RESET_DONE;
-            }
-        } else {
+        uint64_t completed = s.m;
+        if (t.results) {
             for (const auto& p : s.parts) {
                 memcpy(p.sub->dec + p.off, s.dec + p.at, p.count);
                 memcpy(p.sub->rem + p.off, s.rem + p.at, 8 * p.count);
                 memcpy(p.sub->retry + p.off, s.retry + p.at, 8 * p.count);
                 memcpy(p.sub->reset + p.off, s.reset + p.at, 8 * p.count);
+            }
+        } else {
+            // a status: meaningful only when the launch succeeded; RL_RESET_DONE
+            // and RL_REFUND_DONE are the same code
+            completed = 0;
+            if (st == RL_OK) {
+                for (const auto& p : s.parts) memcpy(p.sub->dec + p.off, s.dec + p.at, p.count);
+                for (size_t i = 0; i < s.m; i++) completed += s.dec[i] == RL_RESET_DONE;
             }
         }
         const int64_t now = steady_ns();
@@ -1193,27 +1042,19 @@ void Coalescer::completer() {
             launched_.pop_front();
             inflight_--;
             if (trace_cap_) {
-                BatchTrace t{done_batches_, s.m, 0, s.t_form, s.t_h2d, s.t_launched, t_wait, now};
-                t.t_submit = s.parts.empty() ? s.t_form : s.parts[0].sub->submit_ns;   // the oldest request
-                if (trace_.size() < trace_cap_) trace_.push_back(t);
-                else trace_[done_batches_ % trace_cap_] = t;
+                BatchTrace bt{done_batches_, s.m, 0, s.t_form, s.t_h2d, s.t_launched, t_wait, now};
+                bt.t_submit = s.parts.empty() ? s.t_form : s.parts[0].sub->submit_ns;   // the oldest request
+                if (trace_.size() < trace_cap_) trace_.push_back(bt);
+                else trace_[done_batches_ % trace_cap_] = bt;
             }
             done_batches_++;
-            if (s.is_peek) st_.peeked += s.m;
-            else if (s.is_reset) st_.resets += nreset;
-            else if (s.is_refund) st_.refunds += nreset;
-            else st_.decided += s.m;
+            st_.*t.completed += completed;
             for (const auto& p : s.parts) {
                 Sub* sub = p.sub;
                 if (st != RL_OK && !sub->truncated) sub->status = st;
                 sub->left -= p.count;
                 sub->inflight--;
-                if (sub->left == 0 && !sub->done) {
-                    sub->done = true;
-                    sub->done_ns = now;
-                    if (sub->waiting) sub->cv.notify_all();
-                    notify_locked(sub);
-                }
+                if (sub->left == 0 && !sub->done) finish_locked(sub, now);
                 maybe_free_locked(sub);   // orphaned (its waiter gave up) and now complete
             }
         }
@@ -1343,7 +1184,7 @@ extern "C" int rl_coalescer_decide_deadline(rl_coalescer* c, uint64_t key_id, in
 extern "C" int rl_coalescer_reset(rl_coalescer* c, uint64_t key_id, int64_t ts_ns, uint32_t cfg_id) {
     if (!c) return RL_EINVAL;
     uint64_t t;
-    int rc = c->c->SubmitOp(rlc::OP_RESET, key_id, ts_ns, cfg_id, 0, 0, 0, &t);
+    int rc = c->c->Submit(1, &key_id, &ts_ns, nullptr, &cfg_id, &t, 0, nullptr, rlc::OP_RESET);
     if (rc != RL_OK) return rc;
     // merged with the resets queued next to it: its own status tells whether it ran
     uint8_t status = RL_RESET_DONE;
@@ -1381,87 +1222,73 @@ extern "C" int rl_coalescer_peek(rl_coalescer* c, size_t m, const uint64_t* key_
     return c->c->Wait(t, -1, decision, remaining, retry_after_ns, reset_at_ns);
 }
 
-static int table_op(rl_coalescer* c, rlc::Op op, int64_t now_ms, uint64_t tb, uint64_t win, rl_table_info* out,
-                    const rlc::SnapArgs* snap = nullptr, const rlc::TallyArgs* tally = nullptr,
-                    const rlc::HotArgs* hot = nullptr) {
+static int table_op(rl_coalescer* c, rlc::Op op, const rlc::OpArgs& a, rl_table_info* out = nullptr) {
     uint64_t t;
-    int rc = c->c->SubmitOp(op, 0, 0, 0, now_ms, tb, win, &t, nullptr, snap, tally, hot);
+    int rc = c->c->SubmitOp(op, a, &t);
     if (rc != RL_OK) return rc;
     rl_table_info info{};
     rc = c->c->Wait(t, -1, nullptr, nullptr, nullptr, nullptr, nullptr, &info);
-    if (out && rc == RL_OK) {
-        const uint32_t n = (uint32_t)std::min<size_t>(out->struct_size, sizeof info);   // bytes filled in
-        info.struct_size = n;
-        memcpy(out, &info, n);
-    }
+    if (out && rc == RL_OK) rlc::copy_out_sized(out, info);
     return rc;
 }
 
 extern "C" int rl_coalescer_table_info(rl_coalescer* c, int64_t now_ms, rl_table_info* out) {
     if (!c || !out || out->struct_size < 8) return RL_EINVAL;
-    return table_op(c, rlc::OP_INFO, now_ms, 0, 0, out);
+    rlc::OpArgs a;
+    a.now_ms = now_ms;
+    return table_op(c, rlc::OP_INFO, a, out);
 }
 
 extern "C" int rl_coalescer_gc(rl_coalescer* c, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
                                rl_table_info* out) {
     if (!c || (out && out->struct_size < 8)) return RL_EINVAL;
-    return table_op(c, rlc::OP_GC, now_ms, tb_capacity, win_capacity, out);
+    rlc::OpArgs a;
+    a.now_ms = now_ms;
+    a.cap_tb = tb_capacity;
+    a.cap_win = win_capacity;
+    return table_op(c, rlc::OP_GC, a, out);
 }
 
 extern "C" int rl_coalescer_snapshot(rl_coalescer* c, int64_t now_ms, uint32_t world, uint32_t rank, void* buf,
                                      size_t cap, rl_snapshot_info* out) {
     if (!c || !out || out->struct_size < 8) return RL_EINVAL;
-    rlc::SnapArgs a;
-    a.buf = buf;
-    a.len = cap;
-    a.world = world;
-    a.rank = rank;
-    a.out = out;
-    return table_op(c, rlc::OP_SNAPSHOT, now_ms, 0, 0, nullptr, &a);
+    rlc::OpArgs a;
+    a.now_ms = now_ms;
+    a.snap = {buf, cap, world, rank, out};
+    return table_op(c, rlc::OP_SNAPSHOT, a);
 }
 
 extern "C" int rl_coalescer_restore(rl_coalescer* c, const void* buf, size_t len, int64_t now_ms,
                                     uint64_t tb_capacity, uint64_t win_capacity, rl_table_info* out) {
     if (!c || (out && out->struct_size < 8)) return RL_EINVAL;
-    rlc::SnapArgs a;
-    a.buf = const_cast<void*>(buf);
-    a.len = len;
-    return table_op(c, rlc::OP_RESTORE, now_ms, tb_capacity, win_capacity, out, &a);
+    rlc::OpArgs a;
+    a.now_ms = now_ms;
+    a.cap_tb = tb_capacity;
+    a.cap_win = win_capacity;
+    a.snap.buf = const_cast<void*>(buf);
+    a.snap.len = len;
+    return table_op(c, rlc::OP_RESTORE, a, out);
 }
 
 extern "C" int rl_coalescer_tally(rl_coalescer* c, rl_tally_cfg* cfg_out, size_t cfg_cap, uint32_t* ncfg,
                                   rl_tally_key* key_out, size_t key_cap, uint64_t* keys_tracked, rl_tally_info* info,
                                   int clear) {
     if (!c || !c->c->TallyOn() || (info && info->struct_size < 8)) return RL_EINVAL;
-    rlc::TallyArgs a;
-    a.cfg_out = cfg_out;
-    a.cfg_cap = cfg_cap;
-    a.ncfg = ncfg;
-    a.key_out = key_out;
-    a.key_cap = key_cap;
-    a.keys_tracked = keys_tracked;
-    a.info = info;
-    a.clear = clear;
-    return table_op(c, rlc::OP_TALLY, 0, 0, 0, nullptr, nullptr, &a);
+    rlc::OpArgs a;
+    a.tally = {cfg_out, cfg_cap, ncfg, key_out, key_cap, keys_tracked, info, clear};
+    return table_op(c, rlc::OP_TALLY, a);
 }
 
 extern "C" int rl_coalescer_hot(rl_coalescer* c, rl_hot_key* key_out, size_t key_cap, uint64_t* keys_tracked,
                                 rl_hot_info* info, int clear) {
     if (!c || !c->c->HotOn() || (info && info->struct_size < 8)) return RL_EINVAL;
-    rlc::HotArgs a;
-    a.key_out = key_out;
-    a.key_cap = key_cap;
-    a.keys_tracked = keys_tracked;
-    a.info = info;
-    a.clear = clear;
-    return table_op(c, rlc::OP_HOT, 0, 0, 0, nullptr, nullptr, nullptr, &a);
+    rlc::OpArgs a;
+    a.hot = {key_out, key_cap, keys_tracked, info, clear};
+    return table_op(c, rlc::OP_HOT, a);
 }
 
 extern "C" int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out) {
     if (!c || !out || out->struct_size < 8) return RL_EINVAL;
-    rl_coalescer_stats s = c->c->Stats();
-    const uint32_t n = (uint32_t)std::min<size_t>(out->struct_size, sizeof s);   // bytes filled in
-    s.struct_size = n;
-    memcpy(out, &s, n);
+    rlc::copy_out_sized(out, c->c->Stats());
     return RL_OK;
 }

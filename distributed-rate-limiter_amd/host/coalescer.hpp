@@ -11,6 +11,7 @@
 #pragma once
 
 #include <stdint.h>
+#include <string.h>
 
 #include <condition_variable>
 #include <deque>
@@ -25,8 +26,51 @@
 
 namespace rlc {
 
-// one launch's staging buffers (host side; pinned for the GPU backend)
-struct Slot {
+enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_REFUND, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT, OP_COUNT };
+
+// What the queue, the launch and the counters do with a submission of each
+// operation: stated once here and read everywhere else (a `switch (op)` stays
+// only where the action itself differs: which backend call runs).
+using StatField = uint64_t rl_coalescer_stats::*;
+struct OpTraits {
+    // carries requests through a launch slot (Submit); the others are single
+    // table operations, run synchronously on the submitter thread (SubmitOp)
+    bool batched;
+    bool reads_n;          // `n` is an input (a reset has none)
+    // dec, rem, retry and reset come back; else only a per-request status in
+    // `dec`, which is copied back -- and its RL_RESET_DONE / RL_REFUND_DONE
+    // (one code) counted into `completed` -- only when the launch succeeded
+    bool results;
+    bool merges;           // the run of adjacent same-op submissions at the queue head is one launch
+    bool splits;           // taken in parts of up to max_batch (else whole: m > max_batch is RL_EINVAL)
+    bool queue_cap;        // a full queue refuses it
+    // a decision: the automatic GC budgets it before its launch, the linger
+    // waits for more of it, it counts in submitted / cancelled / expired
+    bool decides;
+    bool counts_batch;     // its launch counts in `batches` ...
+    bool counts_max;       // ... and in `max_batch_seen`
+    StatField launches;    // its own launch counter, if any
+    StatField completed;   // at completion: += m (results), or += the statuses that say done
+    bool keeps_gc_count;   // a table operation that touches no table: the automatic GC's count still holds
+};
+constexpr StatField NO_STAT = nullptr;
+using St = rl_coalescer_stats;
+constexpr OpTraits OPS[OP_COUNT] = {
+    //             batched reads_n results merges splits q_cap  decides batch  max    launches              completed      keeps_gc
+    /* REQ      */ {true,  true,   true,   true,  true,  true,  true,   true,  true,  NO_STAT,              &St::decided,  false},
+    /* RESET    */ {true,  false,  false,  true,  true,  false, false,  true,  false, &St::reset_launches,  &St::resets,   false},
+    /* PEEK     */ {true,  true,   true,   false, true,  true,  false,  false, false, NO_STAT,              &St::peeked,   false},
+    /* REFUND   */ {true,  true,   false,  false, false, true,  false,  false, false, &St::refund_launches, &St::refunds,  false},
+    /* INFO     */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       false},
+    /* GC       */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       false},
+    /* SNAPSHOT */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       false},
+    /* RESTORE  */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       false},
+    /* TALLY    */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       true},
+    /* HOT      */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       true},
+};
+
+// the SoA arrays of one block of requests and results
+struct Arrays {
     uint64_t* key = nullptr;
     int64_t* ts = nullptr;
     int64_t* n = nullptr;
@@ -35,10 +79,28 @@ struct Slot {
     int64_t* rem = nullptr;
     int64_t* retry = nullptr;
     int64_t* reset = nullptr;
+};
+// The one layout of such a block -- a slot's pinned host block, its device
+// block, a host backend's heap block, a submission's buffer --, by capacity:
+// key ts n | cfg | rem retry reset | dec, the result area 64-byte aligned (the
+// device path needs that).  block_bytes(cap) holds it.
+constexpr size_t block_bytes(size_t cap) { return cap * 61 + 64; }
+inline void carve(uint8_t* p, size_t cap, Arrays& a) {
+    a.key = reinterpret_cast<uint64_t*>(p);
+    a.ts = reinterpret_cast<int64_t*>(p + 8 * cap);
+    a.n = reinterpret_cast<int64_t*>(p + 16 * cap);
+    a.cfg = reinterpret_cast<uint32_t*>(p + 24 * cap);
+    uint8_t* q = p + ((28 * cap + 63) & ~size_t(63));
+    a.rem = reinterpret_cast<int64_t*>(q);
+    a.retry = reinterpret_cast<int64_t*>(q + 8 * cap);
+    a.reset = reinterpret_cast<int64_t*>(q + 16 * cap);
+    a.dec = q + 24 * cap;
+}
+
+// one launch's staging buffers (host side; pinned for the GPU backend)
+struct Slot : Arrays {
     size_t m = 0;
-    bool is_reset = false;   // resets (a run of adjacent OP_RESET submissions): key / ts / cfg in, status in `dec`
-    bool is_peek = false;    // read-only queries (one OP_PEEK submission, or a part of it)
-    bool is_refund = false;  // one whole OP_REFUND submission: key / ts / n / cfg in, status in `dec`
+    Op op = OP_REQ;   // of the submissions it was formed from: one operation per launch
     int status = RL_OK;
     int64_t t_form = 0, t_h2d = 0, t_launched = 0;   // steady ns (batch trace)
     struct Part {
@@ -70,32 +132,55 @@ struct HotArgs {
     int clear = 0;
 };
 
+// OP_SNAPSHOT / OP_RESTORE arguments: the caller's buffers (it blocks until
+// the operation is done)
+struct SnapArgs {
+    void* buf = nullptr;              // OP_SNAPSHOT: written; OP_RESTORE: read
+    size_t len = 0;
+    uint32_t world = 1, rank = 0;
+    rl_snapshot_info* out = nullptr;  // OP_SNAPSHOT
+};
+
+// one table operation's arguments (SubmitOp); each operation reads its own
+struct OpArgs {
+    int64_t now_ms = 0;                 // OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE
+    uint64_t cap_tb = 0, cap_win = 0;   // OP_GC, OP_RESTORE
+    SnapArgs snap;                      // OP_SNAPSHOT, OP_RESTORE
+    TallyArgs tally;                    // OP_TALLY
+    HotArgs hot;                        // OP_HOT
+};
+
+// Hand a versioned struct (its first field: uint32_t struct_size) to a caller
+// that may have been compiled with a shorter one: the bytes the caller's
+// struct_size covers, with struct_size = the bytes filled in.
+template <class T>
+inline void copy_out_sized(T* out, T v) {
+    v.struct_size = (uint32_t)(out->struct_size < sizeof v ? out->struct_size : sizeof v);
+    memcpy(out, &v, v.struct_size);
+}
+
 // where batches go: the GPU engine, or synchronous host functions (tests)
 class Backend {
 public:
     virtual ~Backend() = default;
     // usage tally (rl_coalescer_opts.tally_key_slots): once enabled, launch()
-    // counts every batch behind its decisions, before wait(slot) returns
+    // counts every OP_REQ batch behind its decisions, before wait(slot) returns
     virtual int tally_enable(uint32_t key_slots) = 0;
     // rl_tally_read: every batch launched so far is counted (synchronous)
     virtual int tally_read(const TallyArgs& a) = 0;
     // top keys (rl_coalescer_opts.hot_min): once enabled, launch() counts every
-    // batch behind its decisions (and behind its tally), as one rl_hot_batch call
+    // OP_REQ batch behind its decisions (and behind its tally), as one rl_hot_batch call
     virtual int hot_enable(const rl_hot_opts& o) = 0;
     // rl_hot_read: every batch launched so far is counted (synchronous)
     virtual int hot_read(const HotArgs& a) = 0;
     virtual int init(int nslots, size_t max_batch, std::vector<Slot>* slots) = 0;
-    virtual int launch(int slot, Slot& s) = 0;   // asynchronous
-    // the slot's s.m resets (key, ts, cfg; rl_reset_batch_device) after every
-    // launched batch and before every later one, asynchronous like a launch
-    // (completes through wait(slot)); per-request status into s.dec
-    virtual int launch_reset_batch(int slot, Slot& s) = 0;
-    // read-only queries (rl_peek_batch_device) on the slot's staging arrays,
-    // ordered and completed like a launch
-    virtual int launch_peek(int slot, Slot& s) = 0;
-    // one refund call (rl_refund_batch_device) on the slot's s.m requests,
-    // ordered and completed like a launch; per-request status into s.dec
-    virtual int launch_refund(int slot, Slot& s) = 0;
+    // The slot's s.m requests of operation s.op, asynchronous: after every
+    // launch before it and before every later one, completed through
+    // wait(slot).  OP_REQ: decisions (rl_decide_batch_device); OP_PEEK:
+    // read-only queries (rl_peek_batch_device); OP_RESET: resets (key, ts, cfg;
+    // rl_reset_batch_device) and OP_REFUND: one refund call
+    // (rl_refund_batch_device), both with the per-request status into s.dec
+    virtual int launch(int slot, Slot& s) = 0;
     virtual int wait(int slot, Slot& s) = 0;     // until launch `slot` completed
     // synchronous table operations (the GPU engine drains its batches first)
     virtual int table_info(int64_t now_ms, rl_table_info* out) = 0;
@@ -119,27 +204,8 @@ public:
 std::unique_ptr<Backend> make_gpu_backend(rl_engine* e);
 std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b);
 
-enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_REFUND, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT };
-// submissions that carry requests and results (the rest carry one operation)
-inline bool has_requests(Op op) { return op == OP_REQ || op == OP_PEEK; }
-// submissions the submitter takes from the queue in parts of up to max_batch:
-// requests and results, or resets (key / ts / cfg) and their status in `dec`;
-// a refund submission is taken whole
-inline bool is_batched(Op op) { return op <= OP_REFUND; }
-// the synchronous table operations (run_table_op)
-inline bool is_table_op(Op op) { return op >= OP_INFO; }
-
-// OP_SNAPSHOT / OP_RESTORE arguments: the caller's buffers (it blocks until
-// the operation is done)
-struct SnapArgs {
-    void* buf = nullptr;              // OP_SNAPSHOT: written; OP_RESTORE: read
-    size_t len = 0;
-    uint32_t world = 1, rank = 0;
-    rl_snapshot_info* out = nullptr;  // OP_SNAPSHOT
-};
-
 // one submission: its requests (copied) and results, or one table operation
-struct Sub {
+struct Sub : Arrays {
     uint64_t first = 0;
     size_t m = 0, taken = 0, left = 0;
     int status = RL_OK;
@@ -156,22 +222,13 @@ struct Sub {
     int64_t done_ns = 0;          // steady clock at completion
     int64_t submit_ns = 0;        // steady clock at Submit (batch trace)
     void* tag = nullptr;          // the caller's completion tag (SetNotify)
-    // OP_INFO / OP_GC arguments and result
-    int64_t now_ms = 0;
-    uint64_t cap_tb = 0, cap_win = 0;
-    rl_table_info info{};
-    SnapArgs snap;
-    TallyArgs tally;              // OP_TALLY
-    HotArgs hot;                  // OP_HOT
+    OpArgs args;                  // a table operation's arguments ...
+    rl_table_info info{};         // ... and the result of OP_INFO / OP_GC / OP_RESTORE
     std::condition_variable cv;
     std::unique_ptr<uint8_t[]> mem;
-    uint64_t* key;
-    int64_t *ts, *n, *rem, *retry, *reset;
-    uint32_t* cfg;
-    uint8_t* dec;
     size_t cap = 0;               // requests the buffer holds (pooled Subs are reused)
     explicit Sub(size_t m);
-    void carve(size_t m);         // reset for a new submission of m <= cap requests
+    void renew(size_t m);         // reset for a new submission of m <= cap requests
 };
 
 int64_t steady_ns();
@@ -192,20 +249,19 @@ public:
     ~Coalescer();
     int start();
     // tag: with SetNotify, the completion callback receives it
-    // op: OP_REQ, or OP_PEEK -- read-only queries, queued in sequence order
-    // like a Reset and launched on their own (not merged with requests or
-    // with other peeks); not counted in submitted / decided --, or OP_RESET:
-    // m resets (n is not read), merged with the reset submissions next to it
-    // in the queue into one launch; Wait's `dec` receives their status; or
-    // OP_REFUND: one refund call of m <= max_batch requests, launched whole
-    // and on its own; Wait's `dec` receives the status
+    // op: one with OPS[op].batched.  OP_REQ, or OP_PEEK -- read-only queries,
+    // queued in sequence order like a Reset and launched on their own (not
+    // merged with requests or with other peeks); not counted in submitted /
+    // decided --, or OP_RESET: m resets (n is not read), merged with the reset
+    // submissions next to it in the queue into one launch; Wait's `dec`
+    // receives their status; or OP_REFUND: one refund call of m <= max_batch
+    // requests, launched whole and on its own; Wait's `dec` receives the status
     int Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
                uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr, Op op = OP_REQ);
-    // a single Reset (an OP_RESET submission of one) / table count / table GC /
-    // snapshot / restore, queued in sequence order
-    int SubmitOp(Op op, uint64_t key, int64_t ts, uint32_t cfg, int64_t now_ms, uint64_t cap_tb,
-                 uint64_t cap_win, uint64_t* ticket, void* tag = nullptr, const SnapArgs* snap = nullptr,
-                 const TallyArgs* tally = nullptr, const HotArgs* hot = nullptr);
+    // one table operation (an op without OPS[op].batched: table count, table
+    // GC, snapshot, restore, tally read, top-keys read), queued in sequence
+    // order; never refused by a full queue
+    int SubmitOp(Op op, const OpArgs& a, uint64_t* ticket, void* tag = nullptr);
     // rl_coalescer_opts.tally_key_slots != 0
     bool TallyOn() const { return o_.tally_key_slots != 0; }
     // rl_coalescer_opts.hot_min != 0
@@ -234,17 +290,36 @@ public:
 private:
     void submitter();
     void completer();
-    // drop a submission none of whose requests was launched: done, unapplied
-    void drop_locked(Sub* s, int code);
-    // a submission split across launches whose context ended: drop the part
-    // not launched yet (never applied); the launched part completes as usual
-    void truncate_locked(Sub* s, int code);
-    // a submission became done (lock held): the completion callback
+    // queue `s`, filled in but for its ticket, as `m` pending requests (a
+    // table operation: 1); refused -- and released -- when the coalescer is
+    // closed or, for an operation a full queue refuses, the queue is full
+    int enqueue(Sub* s, size_t m, uint64_t* ticket);
+    // The part of `s` not launched yet ends with `code` (its deadline passed,
+    // or it was cancelled) and is never applied.  Nothing launched: the
+    // submission is dropped, done.  A submission split across launches, partly
+    // launched (applied, as an EVAL already sent): that part completes as
+    // usual, and the submitter pops the submission when it reaches the head
+    // of the queue (taken = m stops it)
+    void end_unlaunched_locked(Sub* s, int code);
+    // a submission became done at `now` (lock held): its waiter and the completion callback
+    void finish_locked(Sub* s, int64_t now) {
+        s->done = true;
+        s->done_ns = now;
+        if (s->waiting) s->cv.notify_all();
+        notify_locked(s);
+    }
     void notify_locked(Sub* s) {
         if (notify_ && s->tag) notify_(notify_user_, s->first, s->tag);
     }
     NotifyFn notify_ = nullptr;
     void* notify_user_ = nullptr;
+    // the submitter takes the queue's first submission off it (lock held)
+    Sub* pop_front_locked() {
+        Sub* s = queue_.front();
+        queue_.pop_front();
+        s->in_queue = false;
+        return s;
+    }
     // free a submission no one references any more (queue, slots, caller)
     void maybe_free_locked(Sub* s);
     // automatic GC before launching `s` (submitter thread, lock not held)

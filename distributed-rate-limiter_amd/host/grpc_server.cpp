@@ -229,10 +229,48 @@ struct Conn;
 // K_PEEK: a read-only AllowN (rl_coalescer_peek); K_RESET_BATCH: many resets, one coalescer submission;
 // K_USAGE: RateLimiterMetrics.Usage, one rl_coalescer_tally; K_TOPKEYS: RateLimiterTopKeys.TopKeys, one
 // rl_coalescer_hot; K_REFUND / K_REFUND_BATCH: RateLimiterRefund, one refund submission (rl_coalescer_refund)
-enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE, K_TOPKEYS, K_REFUND, K_REFUND_BATCH };
+enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE, K_TOPKEYS, K_REFUND, K_REFUND_BATCH, K_COUNT };
+
+// What each kind of RPC asks of the coalescer and how it reports, stated once.
+struct KindTraits {
+    rlc::Op op;         // the coalescer operation it submits
+    // the RPC's deadline is the submission's (queued, expired and cancelled
+    // like an Allow); else it has none: once queued it is applied (a reset, a
+    // refund)
+    bool deadline;
+    bool decides;       // its requests count in the server's `decisions`
+    const char* fail;   // what an engine error's message begins with
+    const char* off;    // a queued read: the message when the feature is off
+    // a repeated-Request message (dispatch_batch): what a malformed one is
+    // answered with; n <= 0 is the item's error; the time is just inside the
+    // window whose reset time the client passes back (window_reset_at_unix_ns),
+    // or now; the keys' names are kept (Server::keep_names)
+    const char* bad;
+    bool needs_n, takes_at, names;
+};
+constexpr KindTraits KINDS[K_COUNT] = {
+    /* K_ALLOW        */ {rlc::OP_REQ, true, true, "failed to check rate limit: ", nullptr,
+                          nullptr, false, false, false},
+    /* K_BATCH        */ {rlc::OP_REQ, true, true, "failed to check rate limit: ", nullptr,
+                          "bad AllowBatchRequest", true, false, true},
+    /* K_RESET        */ {rlc::OP_RESET, false, false, "failed to reset rate limit: ", nullptr,
+                          nullptr, false, false, false},
+    /* K_PEEK         */ {rlc::OP_PEEK, true, false, "failed to check rate limit: ", nullptr,
+                          nullptr, false, false, false},
+    /* K_RESET_BATCH  */ {rlc::OP_RESET, false, false, "failed to reset rate limit: ", nullptr,
+                          "bad ResetBatchRequest", false, false, false},
+    /* K_USAGE        */ {rlc::OP_TALLY, false, false, "failed to read usage: ", "usage tally is off",
+                          nullptr, false, false, false},
+    /* K_TOPKEYS      */ {rlc::OP_HOT, false, false, "failed to read top keys: ", "top keys are off",
+                          nullptr, false, false, false},
+    /* K_REFUND       */ {rlc::OP_REFUND, false, false, "failed to refund rate limit: ", nullptr,
+                          nullptr, false, false, false},
+    /* K_REFUND_BATCH */ {rlc::OP_REFUND, false, false, "failed to refund rate limit: ", nullptr,
+                          "bad RefundBatchRequest", true, true, false},
+};
 // a queued read that writes into buffers its Rpc owns: not cancelled when its
 // client goes away, but detached and left to finish
-inline bool is_read(Kind k) { return k == K_USAGE || k == K_TOPKEYS; }
+inline bool is_read(Kind k) { return !rlc::OPS[KINDS[k].op].batched; }
 
 // what a Usage RPC's tally read writes into (OP_TALLY runs on the submitter
 // thread): owned by the Rpc, which stays in its loop's table until the read is
@@ -263,7 +301,6 @@ struct Stream {
 
 struct BatchItem {
     const Limiter* lim;
-    int64_t n;
     int err;                   // 0: submitted; 1: unknown limiter; 2: invalid n
     std::string name;          // the unknown limiter's name
     std::string key;           // Rpc.named: the key's name (remembered if it is denied or watched)
@@ -540,169 +577,167 @@ Outcome decide_outcome(const Limiter* lim, int64_t t, int rc, uint8_t dec, int64
         return o;
     }
     o.code = code;
-    o.r.error = "failed to check rate limit: " + err;
+    o.r.error = KINDS[K_ALLOW].fail + err;
     return o;
+}
+
+// the limiter's name of a result row (field 1), by its config id
+void put_limiter_name(std::string& o, const Server* s, uint32_t cfg) {
+    for (const Limiter& l : s->lims)
+        if (l.cfg == cfg) return put_bytes(o, 1, l.name);
+}
+
+void put_usage(std::string& msg, Server* s, const UsageBuf& u) {
+    std::string one;
+    for (const Limiter& l : s->lims) {       // UsageResponse.limiters = 1
+        one.clear();
+        put_bytes(one, 1, l.name);
+        if (l.cfg < u.ncfg && l.cfg < u.rows.size()) {
+            const rl_tally_cfg& r = u.rows[l.cfg];
+            put_int(one, 2, (int64_t)r.count[RL_ALLOWED]);
+            put_int(one, 3, (int64_t)r.count[RL_DENIED]);
+            put_int(one, 4, (int64_t)r.count[RL_ERROR]);
+            put_int(one, 5, (int64_t)r.count[RL_INVALID]);
+            put_int(one, 6, (int64_t)r.units[1]);
+            put_int(one, 7, (int64_t)r.units[0]);
+        }
+        put_msg(msg, 1, one);
+    }
+    const size_t nk = (size_t)std::min<uint64_t>(u.keys.size(), u.tracked);
+    for (size_t i = 0; i < nk; i++) {        // UsageResponse.keys = 2
+        const rl_tally_key& k = u.keys[i];
+        one.clear();
+        put_limiter_name(one, s, k.cfg_id);
+        put_fixed64(one, 2, k.key_id);
+        put_bytes(one, 3, s->name_of(k.key_id));
+        put_int(one, 4, (int64_t)k.denied);
+        put_int(one, 5, (int64_t)k.units_denied);
+        put_msg(msg, 2, one);
+    }
+    put_int(msg, 3, (int64_t)u.info.untracked_requests);
+    put_int(msg, 4, (int64_t)u.tracked);
+}
+
+void put_topkeys(std::string& msg, Server* s, const HotBuf& h) {
+    const size_t nk = (size_t)std::min<uint64_t>(h.keys.size(), h.tracked);
+    std::string one;
+    for (size_t i = 0; i < nk; i++) {        // TopKeysResponse.keys = 1
+        const rl_hot_key& k = h.keys[i];
+        one.clear();
+        put_limiter_name(one, s, k.cfg_id);
+        put_fixed64(one, 2, k.key_id);
+        put_bytes(one, 3, s->name_of(k.key_id));
+        put_int(one, 4, (int64_t)k.estimate);
+        put_msg(msg, 1, one);
+    }
+    put_int(msg, 2, (int64_t)h.info.total);
+    put_int(msg, 3, (int64_t)h.tracked);
+    put_int(msg, 4, (int64_t)h.info.dropped);
+    put_int(msg, 5, (int64_t)h.info.width);
+    put_int(msg, 6, (int64_t)h.info.hot_min);
+    put_int(msg, 7, (int64_t)h.info.weight);
+    s->publish_watch(h.keys.data(), nk);     // this response's keys are watched from now on
+}
+
+// a submission's results: arrays of Rpc.m entries, or none (it was not queued)
+struct Results {
+    const uint8_t* dec = nullptr;
+    const int64_t *rem = nullptr, *retry = nullptr, *reset = nullptr;
+    // a reset's or a refund's status (RL_RESET_DONE and RL_REFUND_DONE are one code)
+    bool done(size_t j) const { return dec && dec[j] == RL_RESET_DONE; }
+};
+
+// the AllowResponse of request j of `lim`; a denied (with the tally on) or
+// watched key's name is remembered
+Outcome allow_outcome(Io* io, const Rpc& rpc, const Limiter* lim, uint64_t id, const std::string& key, int rc,
+                      const Results& r, size_t j) {
+    Server* s = io->srv;
+    if (rpc.named && rc == RL_OK && r.dec && ((r.dec[j] == RL_DENIED && s->tally) || s->watched(io, id)))
+        s->remember(id, key);
+    return decide_outcome(lim, rpc.t, rc, r.dec ? r.dec[j] : 0, r.rem ? r.rem[j] : 0, r.retry ? r.retry[j] : 0,
+                          r.reset ? r.reset[j] : 0);
 }
 
 // ---------------------------------------------------------------------------
 // request dispatch
 // ---------------------------------------------------------------------------
-void finish_rpc(Io* io, uint64_t ticket, Rpc& rpc, int rc, const uint8_t* dec, const int64_t* rem,
-                const int64_t* retry, const int64_t* reset) {
+void finish_rpc(Io* io, Rpc& rpc, int rc, const Results& r = {}) {
     Conn* c = rpc.conn;
     if (!c) return;                       // detached: its stream or its connection went (cb_close, close_conn)
     auto it = c->streams.find(rpc.sid);
     if (it == c->streams.end()) return;   // the client went away
     Stream* st = it->second.get();
     st->pending = false;
+    const KindTraits& k = KINDS[rpc.kind];
+    const auto engine_error = [&k](int code) { return k.fail + ("engine status " + std::to_string(code)); };
+    // an engine error is the RPC's error (a queued read's RL_EINVAL: the feature is off)
+    const auto failed = [&] {
+        if (rc == RL_OK) return false;
+        if (k.off && rc == RL_EINVAL) respond_err(c, st, GRPC_FAILED_PRECONDITION, k.off);
+        else respond_err(c, st, GRPC_UNAVAILABLE, engine_error(rc));
+        return true;
+    };
     std::string msg;
-    if (rpc.kind == K_USAGE) {
-        Server* s = io->srv;
-        if (rc == RL_EINVAL) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "usage tally is off");
-        if (rc != RL_OK) return respond_err(c, st, GRPC_UNAVAILABLE, "failed to read usage: engine status " + std::to_string(rc));
-        const UsageBuf& u = *rpc.usage;
-        std::string one;
-        for (const Limiter& l : s->lims) {       // UsageResponse.limiters = 1
-            one.clear();
-            put_bytes(one, 1, l.name);
-            if (l.cfg < u.ncfg && l.cfg < u.rows.size()) {
-                const rl_tally_cfg& r = u.rows[l.cfg];
-                put_int(one, 2, (int64_t)r.count[RL_ALLOWED]);
-                put_int(one, 3, (int64_t)r.count[RL_DENIED]);
-                put_int(one, 4, (int64_t)r.count[RL_ERROR]);
-                put_int(one, 5, (int64_t)r.count[RL_INVALID]);
-                put_int(one, 6, (int64_t)r.units[1]);
-                put_int(one, 7, (int64_t)r.units[0]);
-            }
-            put_msg(msg, 1, one);
+    switch (rpc.kind) {
+        case K_USAGE:
+            if (failed()) return;
+            put_usage(msg, io->srv, *rpc.usage);
+            break;
+        case K_TOPKEYS:
+            if (failed()) return;
+            put_topkeys(msg, io->srv, *rpc.hot);
+            break;
+        case K_RESET:
+            if (rc == RL_OK && r.dec && !r.done(0)) rc = RL_EINVAL;   // it did not run
+            if (failed()) return;
+            break;
+        case K_REFUND:
+            // a storage error is the RPC's error, never a fail-open answer (as Reset)
+            if (failed()) return;
+            put_int(msg, 1, r.done(0) ? 1 : 0);   // RefundResponse.applied = 1
+            break;
+        case K_ALLOW:
+        case K_PEEK: {
+            const Outcome o = allow_outcome(io, rpc, rpc.lim, rpc.id, rpc.key, rc, r, 0);
+            if (o.code != GRPC_OK) return respond_err(c, st, o.code, o.r.error);
+            put_allow_response(msg, o.r);
+            break;
         }
-        const size_t nk = (size_t)std::min<uint64_t>(u.keys.size(), u.tracked);
-        for (size_t i = 0; i < nk; i++) {        // UsageResponse.keys = 2
-            const rl_tally_key& k = u.keys[i];
-            one.clear();
-            for (const Limiter& l : s->lims)
-                if (l.cfg == k.cfg_id) {
-                    put_bytes(one, 1, l.name);
-                    break;
+        default: {
+            // the batch responses: field 1 repeated, one entry per request of
+            // the RPC (an empty one is an entry too).  AllowBatchResponse: an
+            // AllowResponse; RefundBatchResponse: RefundResult {applied = 1,
+            // error = 2}; ResetBatchResponse: an error string, "" = done
+            size_t j = 0;
+            std::string one;
+            for (const BatchItem& b : rpc.items) {
+                // the request's own error, or the engine's for one that was submitted
+                std::string err = b.err == 1 ? "unknown limiter " + py_repr(b.name) : b.err == 2 ? ERR_INVALID_N : "";
+                one.clear();
+                switch (rpc.kind) {
+                    case K_BATCH: {
+                        Result res;
+                        if (b.err) res.error = err;
+                        else res = allow_outcome(io, rpc, b.lim, b.id, b.key, rc, r, j).r;
+                        put_allow_response(one, res);
+                        break;
+                    }
+                    case K_REFUND_BATCH:
+                        if (!b.err && rc != RL_OK) err = engine_error(rc);
+                        if (!err.empty()) put_bytes(one, 2, err);
+                        else put_int(one, 1, r.done(j) ? 1 : 0);
+                        break;
+                    default: {   // K_RESET_BATCH
+                        const int code = b.err ? RL_OK : rc != RL_OK ? rc : r.done(j) ? RL_OK : RL_EINVAL;
+                        if (code != RL_OK) err = engine_error(code);
+                        one = err;
+                    }
                 }
-            put_fixed64(one, 2, k.key_id);
-            put_bytes(one, 3, s->name_of(k.key_id));
-            put_int(one, 4, (int64_t)k.denied);
-            put_int(one, 5, (int64_t)k.units_denied);
-            put_msg(msg, 2, one);
-        }
-        put_int(msg, 3, (int64_t)u.info.untracked_requests);
-        put_int(msg, 4, (int64_t)u.tracked);
-        return respond_ok(c, st, msg);
-    }
-    if (rpc.kind == K_TOPKEYS) {
-        Server* s = io->srv;
-        if (rc == RL_EINVAL) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "top keys are off");
-        if (rc != RL_OK) return respond_err(c, st, GRPC_UNAVAILABLE, "failed to read top keys: engine status " + std::to_string(rc));
-        const HotBuf& h = *rpc.hot;
-        const size_t nk = (size_t)std::min<uint64_t>(h.keys.size(), h.tracked);
-        std::string one;
-        for (size_t i = 0; i < nk; i++) {        // TopKeysResponse.keys = 1
-            const rl_hot_key& k = h.keys[i];
-            one.clear();
-            for (const Limiter& l : s->lims)
-                if (l.cfg == k.cfg_id) {
-                    put_bytes(one, 1, l.name);
-                    break;
-                }
-            put_fixed64(one, 2, k.key_id);
-            put_bytes(one, 3, s->name_of(k.key_id));
-            put_int(one, 4, (int64_t)k.estimate);
-            put_msg(msg, 1, one);
-        }
-        put_int(msg, 2, (int64_t)h.info.total);
-        put_int(msg, 3, (int64_t)h.tracked);
-        put_int(msg, 4, (int64_t)h.info.dropped);
-        put_int(msg, 5, (int64_t)h.info.width);
-        put_int(msg, 6, (int64_t)h.info.hot_min);
-        put_int(msg, 7, (int64_t)h.info.weight);
-        s->publish_watch(h.keys.data(), nk);     // this response's keys are watched from now on
-        return respond_ok(c, st, msg);
-    }
-    if (rpc.kind == K_REFUND) {
-        // a storage error is the RPC's error, never a fail-open answer (as Reset)
-        if (rc != RL_OK) return respond_err(c, st, GRPC_UNAVAILABLE, "failed to refund rate limit: engine status " + std::to_string(rc));
-        put_int(msg, 1, dec && dec[0] == RL_REFUND_DONE ? 1 : 0);   // RefundResponse.applied = 1
-        return respond_ok(c, st, msg);
-    }
-    if (rpc.kind == K_REFUND_BATCH) {
-        // RefundBatchResponse.results = 1: RefundResult {applied = 1, error = 2} per request
-        size_t j = 0;
-        std::string one;
-        for (const BatchItem& b : rpc.items) {
-            one.clear();
-            if (b.err == 1) put_bytes(one, 2, "unknown limiter " + py_repr(b.name));
-            else if (b.err == 2) put_bytes(one, 2, ERR_INVALID_N);
-            else {
-                if (rc != RL_OK) put_bytes(one, 2, "failed to refund rate limit: engine status " + std::to_string(rc));
-                else put_int(one, 1, dec && dec[j] == RL_REFUND_DONE ? 1 : 0);
-                j++;
+                j += b.err == 0;
+                put_msg(msg, 1, one);
             }
-            put_varint(msg, (1u << 3) | 2);   // an empty result is an entry too
-            put_varint(msg, one.size());
-            msg += one;
         }
-        return respond_ok(c, st, msg);
     }
-    if (rpc.kind == K_RESET_BATCH) {
-        // ResetBatchResponse.errors = 1: one string per request, "" = done
-        size_t j = 0;
-        for (const BatchItem& b : rpc.items) {
-            std::string e;
-            if (b.err == 1) e = "unknown limiter " + py_repr(b.name);
-            else {
-                const int one = rc != RL_OK ? rc : (dec && dec[j] == RL_RESET_DONE) ? RL_OK : RL_EINVAL;
-                if (one != RL_OK) e = "failed to reset rate limit: engine status " + std::to_string(one);
-                j++;
-            }
-            put_varint(msg, (1u << 3) | 2);   // an empty string is an entry too
-            put_varint(msg, e.size());
-            msg += e;
-        }
-        return respond_ok(c, st, msg);
-    }
-    if (rpc.kind == K_RESET) {
-        if (rc == RL_OK && dec && dec[0] != RL_RESET_DONE) rc = RL_EINVAL;
-        if (rc != RL_OK) respond_err(c, st, GRPC_UNAVAILABLE, "failed to reset rate limit: engine status " + std::to_string(rc));
-        else respond_ok(c, st, msg);
-        return;
-    }
-    if (rpc.kind == K_ALLOW && rpc.named && rc == RL_OK && dec &&
-        ((dec[0] == RL_DENIED && io->srv->tally) || io->srv->watched(io, rpc.id)))
-        io->srv->remember(rpc.id, rpc.key);
-    if (rpc.kind == K_ALLOW || rpc.kind == K_PEEK) {
-        const Outcome o = decide_outcome(rpc.lim, rpc.t, rc, dec ? dec[0] : 0, rem ? rem[0] : 0, retry ? retry[0] : 0,
-                                         reset ? reset[0] : 0);
-        if (o.code != GRPC_OK) return respond_err(c, st, o.code, o.r.error);
-        put_allow_response(msg, o.r);
-        return respond_ok(c, st, msg);
-    }
-    size_t j = 0;
-    std::string one;
-    for (const BatchItem& b : rpc.items) {
-        Result r;
-        if (b.err == 1) r.error = "unknown limiter " + py_repr(b.name);
-        else if (b.err == 2) r.error = ERR_INVALID_N;
-        else {
-            if (rpc.named && rc == RL_OK && dec &&
-                ((dec[j] == RL_DENIED && io->srv->tally) || io->srv->watched(io, b.id)))
-                io->srv->remember(b.id, b.key);
-            r = decide_outcome(b.lim, rpc.t, rc, dec ? dec[j] : 0, rem ? rem[j] : 0, retry ? retry[j] : 0,
-                               reset ? reset[j] : 0).r;
-            j++;
-        }
-        one.clear();
-        put_allow_response(one, r);
-        put_varint(msg, (1u << 3) | 2);
-        put_varint(msg, one.size());
-        msg += one;
-    }
-    (void)ticket;
     respond_ok(c, st, msg);
 }
 
@@ -711,40 +746,104 @@ void collect(Io* io, uint64_t ticket) {
     auto it = io->rpcs.find(ticket);
     if (it == io->rpcs.end()) return;   // already collected (a deadline, a cancel)
     Rpc& rpc = it->second;
-    const size_t m = rpc.kind == K_RESET ? 1 : rpc.m;   // a Reset's ticket carries its one status
+    const size_t m = rpc.m;
     std::vector<uint8_t> dec(m);
     std::vector<int64_t> rem(m), retry(m), reset(m);
     const int rc = io->srv->co->Wait(ticket, 0, dec.data(), rem.data(), retry.data(), reset.data());
     if (rc == RL_ETIMEOUT) return;      // not done yet (a spurious wake)
-    finish_rpc(io, ticket, rpc, rc, dec.data(), rem.data(), retry.data(), reset.data());
+    finish_rpc(io, rpc, rc, Results{dec.data(), rem.data(), retry.data(), reset.data()});
     io->rpcs.erase(it);
 }
 
-void submit_rpc(Io* io, Conn* c, Stream* st, Rpc&& rpc, size_t m, const uint64_t* key, const int64_t* ts,
-                const int64_t* n, const uint32_t* cfg) {
-    Server* s = io->srv;
-    rpc.deadline = st->timeout_ns >= 0 && st->timeout_ns < NO_DEADLINE_NS
-                       ? std::max<int64_t>(1, rlc::steady_ns() + st->timeout_ns)   // no overflow below the bound
-                       : 0;
-    uint64_t ticket = 0;
-    int rc;
-    if (rpc.kind == K_RESET) rc = s->co->SubmitOp(rlc::OP_RESET, key[0], ts[0], cfg[0], 0, 0, 0, &ticket, io);
-    // like a Reset, a reset batch has no deadline: once queued it is applied
-    else if (rpc.kind == K_RESET_BATCH) rc = s->co->Submit(m, key, ts, nullptr, cfg, &ticket, 0, io, rlc::OP_RESET);
-    // one RPC is one refund submission: one engine call, applied in sequence order; no deadline, as a reset
-    else if (rpc.kind == K_REFUND || rpc.kind == K_REFUND_BATCH)
-        rc = s->co->Submit(m, key, ts, n, cfg, &ticket, 0, io, rlc::OP_REFUND);
-    else rc = s->co->Submit(m, key, ts, n, cfg, &ticket, rpc.deadline, io, rpc.kind == K_PEEK ? rlc::OP_PEEK : rlc::OP_REQ);
-    // a peek, a reset or a refund decides nothing
-    if (rpc.kind != K_PEEK && rpc.kind != K_RESET_BATCH && rpc.kind != K_REFUND && rpc.kind != K_REFUND_BATCH) s->n_dec += m;
-    if (rc != RL_OK) {   // queue full / closed: the error branch at once
-        finish_rpc(io, 0, rpc, rc, nullptr, nullptr, nullptr, nullptr);
-        return;
-    }
+// the coalescer took the RPC's submission (rc == RL_OK): the loop collects the
+// ticket when the completion hook hands it over, or at the RPC's deadline;
+// else (queue full / closed) the error branch at once
+void await_ticket(Io* io, Stream* st, Rpc&& rpc, int rc, uint64_t ticket) {
+    if (rc != RL_OK) return finish_rpc(io, rpc, rc);
     st->pending = true;
     st->ticket = ticket;
     if (rpc.deadline) io->deadlines.push({rpc.deadline, ticket});
     io->rpcs.emplace(ticket, std::move(rpc));
+}
+
+// one coalescer submission per RPC, completed through the ticket's
+// notification: the event loop never blocks
+void submit_rpc(Io* io, Stream* st, Rpc&& rpc, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                const uint32_t* cfg) {
+    Server* s = io->srv;
+    const KindTraits& k = KINDS[rpc.kind];
+    rpc.deadline = st->timeout_ns >= 0 && st->timeout_ns < NO_DEADLINE_NS
+                       ? std::max<int64_t>(1, rlc::steady_ns() + st->timeout_ns)   // no overflow below the bound
+                       : 0;
+    uint64_t ticket = 0;
+    const int rc = s->co->Submit(rpc.m, key, ts, rlc::OPS[k.op].reads_n ? n : nullptr, cfg, &ticket,
+                                 k.deadline ? rpc.deadline : 0, io, k.op);
+    if (k.decides) s->n_dec += rpc.m;
+    await_ticket(io, st, std::move(rpc), rc, ticket);
+}
+
+// a queued read (Usage, TopKeys): one table operation in the coalescer's
+// sequence, completed like a submission: the event loop does not wait for it
+void submit_read(Io* io, Stream* st, Rpc&& rpc, const rlc::OpArgs& a) {
+    uint64_t ticket = 0;
+    const int rc = io->srv->co->SubmitOp(KINDS[rpc.kind].op, a, &ticket, io);
+    await_ticket(io, st, std::move(rpc), rc, ticket);
+}
+
+// UsageRequest / TopKeysRequest: top = 1 (65536 rows at most), clear = 2
+bool parse_top_clear(std::string_view msg, size_t* top, bool* clear) {
+    Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
+    while (pb.more()) {
+        const uint64_t tag = pb.varint();
+        if ((tag >> 3) == 1 && (tag & 7) == 0) *top = (size_t)std::min<uint64_t>(pb.varint() & 0xffffffffu, 1u << 16);
+        else if ((tag >> 3) == 2 && (tag & 7) == 0) *clear = pb.varint() != 0;
+        else pb.skip((uint32_t)(tag & 7));
+    }
+    return pb.ok;
+}
+
+// AllowBatch, ResetBatch, RefundBatch: a message of repeated requests (field
+// 1) is one submission of those that can run; the others keep their error
+void dispatch_batch(Conn* c, Stream* st, std::string_view msg, Kind kind) {
+    Io* io = c->io;
+    Server* s = io->srv;
+    const KindTraits& k = KINDS[kind];
+    Rpc rpc{c, st->id, kind, s->now(), 0, nullptr, {}, 0};
+    rpc.named = k.names && s->keep_names();
+    std::vector<uint64_t> key;
+    std::vector<int64_t> ts, n;
+    std::vector<uint32_t> cfg;
+    Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
+    while (pb.more()) {
+        const uint64_t tag = pb.varint();
+        if ((tag >> 3) != 1 || (tag & 7) != 2) {
+            pb.skip((uint32_t)(tag & 7));
+            continue;
+        }
+        ReqMsg r;
+        if (!parse_req(pb.bytes(), &r) || !pb.ok) return respond_err(c, st, GRPC_INTERNAL, k.bad);
+        BatchItem it{s->find(r.limiter), 0, {}};
+        if (!it.lim) {
+            it.err = 1;
+            it.name = std::string(r.limiter);
+        } else if (k.needs_n && r.n <= 0) {
+            it.err = 2;
+        } else {
+            key.push_back(s->key_id(it.lim, r.key));
+            ts.push_back(k.takes_at && r.at ? r.at - 1 : rpc.t);
+            n.push_back(r.n);
+            cfg.push_back(it.lim->cfg);
+            if (rpc.named) {
+                it.key = std::string(r.key);
+                it.id = key.back();
+            }
+        }
+        rpc.items.push_back(std::move(it));
+    }
+    if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, k.bad);
+    rpc.m = key.size();
+    if (rpc.m == 0) return finish_rpc(io, rpc, RL_OK);
+    submit_rpc(io, st, std::move(rpc), key.data(), ts.data(), n.data(), cfg.data());
 }
 
 void dispatch(Conn* c, Stream* st) {
@@ -766,39 +865,8 @@ void dispatch(Conn* c, Stream* st) {
         put_int(out, 1, status);
         return respond_ok(c, st, out);
     }
-    if (p == "/ratelimiter.v1.RateLimiterAdmin/ResetBatch") {
-        // one coalescer submission per RPC, completed through the ticket's
-        // notification like every other RPC: the event loop never blocks
-        Rpc rpc{c, st->id, K_RESET_BATCH, s->now(), 0, nullptr, {}, 0};
-        std::vector<uint64_t> key;
-        std::vector<int64_t> ts;
-        std::vector<uint32_t> cfg;
-        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
-        while (pb.more()) {
-            const uint64_t tag = pb.varint();
-            if ((tag >> 3) != 1 || (tag & 7) != 2) {
-                pb.skip((uint32_t)(tag & 7));
-                continue;
-            }
-            ReqMsg r;
-            if (!parse_req(pb.bytes(), &r) || !pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad ResetBatchRequest");
-            BatchItem it{s->find(r.limiter), 0, 0, {}};
-            if (!it.lim) {
-                it.err = 1;
-                it.name = std::string(r.limiter);
-            } else {
-                key.push_back(s->key_id(it.lim, r.key));
-                ts.push_back(rpc.t);
-                cfg.push_back(it.lim->cfg);
-            }
-            rpc.items.push_back(std::move(it));
-        }
-        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad ResetBatchRequest");
-        rpc.m = key.size();
-        if (rpc.m == 0) return finish_rpc(io, 0, rpc, RL_OK, nullptr, nullptr, nullptr, nullptr);
-        const size_t mm = rpc.m;
-        return submit_rpc(io, c, st, std::move(rpc), mm, key.data(), ts.data(), nullptr, cfg.data());
-    }
+    if (p == "/ratelimiter.v1.RateLimiterAdmin/ResetBatch") return dispatch_batch(c, st, msg, K_RESET_BATCH);
+    if (p == "/ratelimiter.v1.RateLimiterRefund/RefundBatch") return dispatch_batch(c, st, msg, K_REFUND_BATCH);
     if (p == "/ratelimiter.v1.RateLimiterRefund/Refund") {
         ReqMsg r;
         if (!parse_req(msg, &r)) return respond_err(c, st, GRPC_INTERNAL, "bad RefundRequest");
@@ -810,116 +878,40 @@ void dispatch(Conn* c, Stream* st) {
         const int64_t now = s->now();
         const int64_t t = r.at ? r.at - 1 : now;
         const uint64_t id = s->key_id(lim, r.key);
-        Rpc rpc{c, st->id, K_REFUND, now, 0, lim, {}, 1};
         const int64_t n = r.n;
         const uint32_t cfg = lim->cfg;
-        return submit_rpc(io, c, st, std::move(rpc), 1, &id, &t, &n, &cfg);
-    }
-    if (p == "/ratelimiter.v1.RateLimiterRefund/RefundBatch") {
-        // one refund submission per RPC (one engine call: refunds of one key and
-        // window are summed), completed through the ticket's notification
-        Rpc rpc{c, st->id, K_REFUND_BATCH, s->now(), 0, nullptr, {}, 0};
-        std::vector<uint64_t> key;
-        std::vector<int64_t> ts, n;
-        std::vector<uint32_t> cfg;
-        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
-        while (pb.more()) {
-            const uint64_t tag = pb.varint();
-            if ((tag >> 3) != 1 || (tag & 7) != 2) {
-                pb.skip((uint32_t)(tag & 7));
-                continue;
-            }
-            ReqMsg r;
-            if (!parse_req(pb.bytes(), &r) || !pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad RefundBatchRequest");
-            BatchItem it{s->find(r.limiter), r.n, 0, {}};
-            if (!it.lim) {
-                it.err = 1;
-                it.name = std::string(r.limiter);
-            } else if (r.n <= 0) {
-                it.err = 2;
-            } else {
-                key.push_back(s->key_id(it.lim, r.key));
-                ts.push_back(r.at ? r.at - 1 : rpc.t);
-                n.push_back(r.n);
-                cfg.push_back(it.lim->cfg);
-            }
-            rpc.items.push_back(std::move(it));
-        }
-        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad RefundBatchRequest");
-        rpc.m = key.size();
-        if (rpc.m == 0) return finish_rpc(io, 0, rpc, RL_OK, nullptr, nullptr, nullptr, nullptr);
-        const size_t mm = rpc.m;
-        return submit_rpc(io, c, st, std::move(rpc), mm, key.data(), ts.data(), n.data(), cfg.data());
+        return submit_rpc(io, st, Rpc{c, st->id, K_REFUND, now, 0, lim, {}, 1}, &id, &t, &n, &cfg);
     }
     if (p == "/ratelimiter.v1.RateLimiterMetrics/Usage") {
-        if (!s->tally || !s->co->TallyOn()) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "usage tally is off");
-        uint64_t top = 0, clear = 0;   // UsageRequest: top = 1, clear = 2
-        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
-        while (pb.more()) {
-            const uint64_t tag = pb.varint();
-            if ((tag >> 3) == 1 && (tag & 7) == 0) top = pb.varint() & 0xffffffffu;
-            else if ((tag >> 3) == 2 && (tag & 7) == 0) clear = pb.varint();
-            else pb.skip((uint32_t)(tag & 7));
-        }
-        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad UsageRequest");
-        // one table operation in the coalescer's sequence, completed through
-        // the ticket's notification: the event loop does not wait for it
+        if (!s->tally || !s->co->TallyOn()) return respond_err(c, st, GRPC_FAILED_PRECONDITION, KINDS[K_USAGE].off);
+        size_t top = 0;
+        bool clear = false;
+        if (!parse_top_clear(msg, &top, &clear)) return respond_err(c, st, GRPC_INTERNAL, "bad UsageRequest");
         Rpc rpc{c, st->id, K_USAGE, 0, 0, nullptr, {}, 0};
         rpc.usage.reset(new UsageBuf());
         UsageBuf& u = *rpc.usage;
         uint32_t rows = 0;
         for (const Limiter& l : s->lims) rows = std::max(rows, l.cfg + 1);
         u.rows.assign(rows, rl_tally_cfg{});
-        u.keys.assign((size_t)std::min<uint64_t>(top, 1u << 16), rl_tally_key{});
+        u.keys.assign(top, rl_tally_key{});
         u.info.struct_size = sizeof u.info;
-        rlc::TallyArgs a;
-        a.cfg_out = u.rows.data();
-        a.cfg_cap = u.rows.size();
-        a.ncfg = &u.ncfg;
-        a.key_out = u.keys.data();
-        a.key_cap = u.keys.size();
-        a.keys_tracked = &u.tracked;
-        a.info = &u.info;
-        a.clear = clear != 0;
-        uint64_t ticket = 0;
-        const int rc = s->co->SubmitOp(rlc::OP_TALLY, 0, 0, 0, 0, 0, 0, &ticket, io, nullptr, &a);
-        if (rc != RL_OK) return finish_rpc(io, 0, rpc, rc, nullptr, nullptr, nullptr, nullptr);
-        st->pending = true;
-        st->ticket = ticket;
-        io->rpcs.emplace(ticket, std::move(rpc));
-        return;
+        rlc::OpArgs a;
+        a.tally = {u.rows.data(), u.rows.size(), &u.ncfg, u.keys.data(), u.keys.size(), &u.tracked, &u.info, clear};
+        return submit_read(io, st, std::move(rpc), a);
     }
     if (p == "/ratelimiter.v1.RateLimiterTopKeys/TopKeys") {
-        if (!s->hot) return respond_err(c, st, GRPC_FAILED_PRECONDITION, "top keys are off");
-        uint64_t top = 0, clear = 0;   // TopKeysRequest: top = 1, clear = 2
-        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
-        while (pb.more()) {
-            const uint64_t tag = pb.varint();
-            if ((tag >> 3) == 1 && (tag & 7) == 0) top = pb.varint() & 0xffffffffu;
-            else if ((tag >> 3) == 2 && (tag & 7) == 0) clear = pb.varint();
-            else pb.skip((uint32_t)(tag & 7));
-        }
-        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad TopKeysRequest");
-        // as Usage: one table operation in the coalescer's sequence, completed
-        // through the ticket's notification
+        if (!s->hot) return respond_err(c, st, GRPC_FAILED_PRECONDITION, KINDS[K_TOPKEYS].off);
+        size_t top = 0;
+        bool clear = false;
+        if (!parse_top_clear(msg, &top, &clear)) return respond_err(c, st, GRPC_INTERNAL, "bad TopKeysRequest");
         Rpc rpc{c, st->id, K_TOPKEYS, 0, 0, nullptr, {}, 0};
         rpc.hot.reset(new HotBuf());
         HotBuf& h = *rpc.hot;
-        h.keys.assign((size_t)std::min<uint64_t>(top, 1u << 16), rl_hot_key{});
+        h.keys.assign(top, rl_hot_key{});
         h.info.struct_size = sizeof h.info;
-        rlc::HotArgs a;
-        a.key_out = h.keys.data();
-        a.key_cap = h.keys.size();
-        a.keys_tracked = &h.tracked;
-        a.info = &h.info;
-        a.clear = clear != 0;
-        uint64_t ticket = 0;
-        const int rc = s->co->SubmitOp(rlc::OP_HOT, 0, 0, 0, 0, 0, 0, &ticket, io, nullptr, nullptr, &a);
-        if (rc != RL_OK) return finish_rpc(io, 0, rpc, rc, nullptr, nullptr, nullptr, nullptr);
-        st->pending = true;
-        st->ticket = ticket;
-        io->rpcs.emplace(ticket, std::move(rpc));
-        return;
+        rlc::OpArgs a;
+        a.hot = {h.keys.data(), h.keys.size(), &h.tracked, &h.info, clear};
+        return submit_read(io, st, std::move(rpc), a);
     }
     static const std::string peek_path = "/ratelimiter.v1.RateLimiterStatus/Peek";
     const bool is_peek = p == peek_path;
@@ -937,8 +929,7 @@ void dispatch(Conn* c, Stream* st) {
         if (is_peek && r.n < 0) return respond_err(c, st, GRPC_INVALID_ARGUMENT, ERR_INVALID_N);
         const int64_t t = s->now();
         const uint64_t id = s->key_id(lim, r.key);
-        const size_t mm = m == "Reset" ? 0 : 1;
-        Rpc rpc{c, st->id, m == "Reset" ? K_RESET : is_peek ? K_PEEK : K_ALLOW, t, 0, lim, {}, mm};
+        Rpc rpc{c, st->id, m == "Reset" ? K_RESET : is_peek ? K_PEEK : K_ALLOW, t, 0, lim, {}, 1};
         if (rpc.kind == K_ALLOW && s->keep_names()) {
             rpc.named = true;
             rpc.key = std::string(r.key);
@@ -946,47 +937,9 @@ void dispatch(Conn* c, Stream* st) {
         }
         const int64_t n = r.n;
         const uint32_t cfg = lim->cfg;
-        return submit_rpc(io, c, st, std::move(rpc), mm, &id, &t, &n, &cfg);
+        return submit_rpc(io, st, std::move(rpc), &id, &t, &n, &cfg);
     }
-    if (m == "AllowBatch") {
-        Rpc rpc{c, st->id, K_BATCH, s->now(), 0, nullptr, {}, 0};
-        rpc.named = s->keep_names();
-        std::vector<uint64_t> key;
-        std::vector<int64_t> ts, n;
-        std::vector<uint32_t> cfg;
-        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
-        while (pb.more()) {
-            const uint64_t tag = pb.varint();
-            if ((tag >> 3) != 1 || (tag & 7) != 2) {
-                pb.skip((uint32_t)(tag & 7));
-                continue;
-            }
-            ReqMsg r;
-            if (!parse_req(pb.bytes(), &r) || !pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad AllowBatchRequest");
-            BatchItem it{s->find(r.limiter), r.n, 0, {}};
-            if (!it.lim) {
-                it.err = 1;
-                it.name = std::string(r.limiter);
-            } else if (r.n <= 0) {
-                it.err = 2;
-            } else {
-                key.push_back(s->key_id(it.lim, r.key));
-                ts.push_back(rpc.t);
-                n.push_back(r.n);
-                cfg.push_back(it.lim->cfg);
-                if (rpc.named) {
-                    it.key = std::string(r.key);
-                    it.id = key.back();
-                }
-            }
-            rpc.items.push_back(std::move(it));
-        }
-        if (!pb.ok) return respond_err(c, st, GRPC_INTERNAL, "bad AllowBatchRequest");
-        rpc.m = key.size();
-        if (rpc.m == 0) return finish_rpc(io, 0, rpc, RL_OK, nullptr, nullptr, nullptr, nullptr);
-        const size_t mm = rpc.m;
-        return submit_rpc(io, c, st, std::move(rpc), mm, key.data(), ts.data(), n.data(), cfg.data());
-    }
+    if (m == "AllowBatch") return dispatch_batch(c, st, msg, K_BATCH);
     respond_err(c, st, GRPC_UNIMPLEMENTED, "unknown method " + m);
 }
 
