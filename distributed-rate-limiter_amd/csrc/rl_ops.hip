@@ -1,4 +1,4 @@
-// rl_ops.hip -- Peek and Reset (single, batched, routed) and Refund: the
+// rl_ops.hip -- Peek, Reset and Refund (single, batched, routed): the
 // kernels of rl_peek.h, rl_reset.h and rl_refund.h and their C entry points.
 // Each is one chain op -- one kernel, Refund's two -- on the engine's `chain`
 // stream between two replays (chain_op, rl_engine_impl.h).
@@ -68,9 +68,14 @@ static int run_routed_op(rl_engine* e, bool reset, size_t m_max, const RoutedIo&
     });
 }
 
-// the C-ABI of both routed steps: argument checks as rl_decide_routed_device_io
+static int run_refund_routed(rl_engine* e, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
+                             hipEvent_t done);
+
+enum RoutedKind { ROUTED_PEEK, ROUTED_RESET, ROUTED_REFUND };
+
+// the C-ABI of the routed steps: argument checks as rl_decide_routed_device_io
 // / _ev, except that m_max is bounded by the 32-bit `order` only
-static int routed_op_entry(rl_engine* e, bool reset, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+static int routed_op_entry(rl_engine* e, RoutedKind kind, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
                            const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
                            void* out_stream, void* done_event) {
     if (!e || !count || (m_max && (!recv || !order || !server_ms || !res))) return RL_EINVAL;
@@ -82,24 +87,37 @@ static int routed_op_entry(rl_engine* e, bool reset, size_t m_max, const uint32_
         return RL_OK;
     }
     const RoutedIo io{recv, order, count, server_ms, res, e->d_eflags};
-    return run_routed_op(e, reset, m_max, io, s, out_stream ? (hipStream_t)out_stream : s, (hipEvent_t)done_event);
+    hipStream_t so = out_stream ? (hipStream_t)out_stream : s;
+    if (kind == ROUTED_REFUND) return run_refund_routed(e, m_max, io, s, so, (hipEvent_t)done_event);
+    return run_routed_op(e, kind == ROUTED_RESET, m_max, io, s, so, (hipEvent_t)done_event);
 }
 
 extern "C" int rl_peek_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
                                      const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
                                      void* in_stream, void* out_stream, void* done_event) {
-    return routed_op_entry(e, false, m_max, count, recv, order, server_ms, res, in_stream, out_stream, done_event);
+    return routed_op_entry(e, ROUTED_PEEK, m_max, count, recv, order, server_ms, res, in_stream, out_stream,
+                           done_event);
 }
 
 extern "C" int rl_reset_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
                                       const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
                                       void* in_stream, void* out_stream, void* done_event) {
-    return routed_op_entry(e, true, m_max, count, recv, order, server_ms, res, in_stream, out_stream, done_event);
+    return routed_op_entry(e, ROUTED_RESET, m_max, count, recv, order, server_ms, res, in_stream, out_stream,
+                           done_event);
+}
+
+extern "C" int rl_refund_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                                       const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
+                                       void* in_stream, void* out_stream, void* done_event) {
+    return routed_op_entry(e, ROUTED_REFUND, m_max, count, recv, order, server_ms, res, in_stream, out_stream,
+                           done_event);
 }
 
 // The routed peek and reset steps on an empty batch (they read the zero count
 // and nothing else), then k_peek and k_reset_batch on one request that is
 // rejected: no config is registered yet.  The staging arrays hold zeros.
+// No refund kernel is launched here, routed or not: the first refund of an
+// engine allocates its scratch, and the warm-up allocates nothing.
 int rl::ops_warm_up(rl_engine* e) {
     hipStream_t s = e->stream;
     const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
@@ -253,6 +271,32 @@ static int run_refund(rl_engine* e, size_t m, const uint64_t* key, const int64_t
         k_refund_add<<<grid, REFUND_BLOCK, 0, c>>>((uint64_t)m, key, ts, n, cfg, sms, status, e->d_cfg, ncfg, e->d_tb,
                                                    e->tb_cap - 1, e->d_win, e->win_cap - 1, e->spill(), e->profile, S,
                                                    parity);
+        k_refund_apply<<<grid, REFUND_BLOCK, 0, c>>>(e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1,
+                                                     e->spill(), e->profile, S, parity);
+    });
+}
+
+// enqueue the refund step of the routed path (include/rl_route.h): the merged
+// batch as ONE refund call -- k_refund_add_routed over the first B = min(m_max,
+// refund_max) requests, then k_refund_apply, one chain op ordered like
+// run_refund.  The kernels always wait for s (count, order and the store clocks
+// are the merge's outputs there); their end is recorded into `done` when given,
+// else so waits for it.  The scratch and the call parity are the array form's;
+// no stream of its own; nothing is counted in rl_stats; the one flag it can
+// raise is EF_ROUTED_OVER (a count above B).
+static int run_refund_routed(rl_engine* e, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
+                             hipEvent_t done) {
+    RefundScratch S;
+    const int r = refund_scratch(e, &S);
+    if (r != RL_OK) return r;
+    const size_t B = std::min<size_t>(m_max, refund_max(e));
+    const uint32_t parity = (uint32_t)(e->refund_calls++ & 1);
+    const uint32_t ncfg = (uint32_t)e->h_cfg.size();
+    return chain_op(e, s, false, so, e->ev_refund, done, [&](hipStream_t c) {
+        const int grid = grid_for(B, REFUND_BLOCK, REFUND_GRID);
+        k_refund_add_routed<<<grid, REFUND_BLOCK, 0, c>>>((uint64_t)B, (uint64_t)m_max, io, e->d_cfg, ncfg, e->d_tb,
+                                                          e->tb_cap - 1, e->d_win, e->win_cap - 1, e->spill(),
+                                                          e->profile, S, parity);
         k_refund_apply<<<grid, REFUND_BLOCK, 0, c>>>(e->d_cfg, ncfg, e->d_tb, e->tb_cap - 1, e->d_win, e->win_cap - 1,
                                                      e->spill(), e->profile, S, parity);
     });

@@ -35,6 +35,9 @@
 // table.
 // k_refund_apply: one thread per claimed record.  Rebuild N with saturation,
 // do the store above -- the only write to table memory -- and free the record.
+// k_refund_add_routed: k_refund_add over the merged batch of a routed step
+// (rl_routed.h), the same text (refund_requests<RT>); k_refund_apply follows
+// it unchanged.
 //
 // No spin-wait; every loop is bounded by 64, MAX_PROBES, the table masks or
 // m; no CAS loop on table words.  A key a later batch's grouping is inserting
@@ -45,6 +48,7 @@
 // k_refund_apply, so its stores race with nothing.
 #pragma once
 
+#include "rl_routed.h"
 #include "rl_semantics.h"
 #include "rl_table.h"
 #include "rl_window.h"
@@ -149,20 +153,33 @@ __device__ inline void refund_upsert(const RefundScratch& S, uint32_t parity, ui
     }
 }
 
-__global__ __launch_bounds__(REFUND_BLOCK) void k_refund_add(uint64_t m, const uint64_t* __restrict__ key,
-                                                             const int64_t* __restrict__ ts,
-                                                             const int64_t* __restrict__ n,
-                                                             const uint32_t* __restrict__ cfg,
-                                                             const int64_t* __restrict__ sms,
-                                                             uint8_t* __restrict__ status,
-                                                             const CfgDev* __restrict__ cfgs, uint32_t ncfg,
-                                                             const TbEntry* tb, uint64_t tb_mask, const WinEntry* win,
-                                                             uint64_t win_mask, Spill spill, int32_t profile,
-                                                             RefundScratch S, uint32_t parity) {
+// The text of k_refund_add and k_refund_add_routed.  RT selects where a
+// request's fields come from and where its status goes; validation, the
+// locate, the ballot rounds, the upsert and the parity word are the one text
+// between.  RT = false: m refunds as arrays in the caller's order, a status
+// byte each (nullable), a nullable store clock.  RT = true: the merged batch of
+// a routed step (rl_routed.h) -- m is the bound B = min(m_max, rl_refund_max),
+// the size is in device memory, the store clock is the merge's, and the status
+// goes out as one rl_route_res {status, 0, 0, 0} at the receive index.
+template <bool RT>
+__device__ __forceinline__ void refund_requests(uint64_t m, const uint64_t* __restrict__ key,
+                                                const int64_t* __restrict__ ts, const int64_t* __restrict__ n,
+                                                const uint32_t* __restrict__ cfg, const int64_t* __restrict__ sms,
+                                                uint8_t* __restrict__ status, const RoutedIo& io, uint64_t m_max,
+                                                const CfgDev* __restrict__ cfgs, uint32_t ncfg, const TbEntry* tb,
+                                                uint64_t tb_mask, const WinEntry* win, uint64_t win_mask,
+                                                const Spill& spill, int32_t profile, const RefundScratch& S,
+                                                uint32_t parity) {
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
     // the other call parity's list length: that call's k_refund_apply is done
     if (blockIdx.x == 0 && tid == 0) S.cnt[parity ^ 1u] = 0;
+    const uint64_t bound = m;
+    RoutedForm f{};
+    if (RT) {
+        f = routed_open(bound, io);   // a count above B raises EF_ROUTED_OVER
+        m = f.m;                      // min(B, *count): the same in every thread
+    }
     // block-uniform trip count: every lane of a wave stays in the loop, so the
     // ballots and shuffles below see all 64 lanes
     for (uint64_t base = blockIdx.x * (uint64_t)REFUND_BLOCK; base < m; base += (uint64_t)gridDim.x * REFUND_BLOCK) {
@@ -170,19 +187,27 @@ __global__ __launch_bounds__(REFUND_BLOCK) void k_refund_add(uint64_t m, const u
         uint64_t k = 0, code = 0;
         int64_t ws = 0, nn = 0;
         if (i < m) {
-            k = key[i];
-            nn = n[i];
-            const uint32_t c = cfg[i];
+            uint32_t c, at = 0;
+            int64_t tq = 0, clock = 0;
+            if (RT) {
+                const rl_route_rec q = routed_request(io, f, i, at, clock);
+                k = q.key; nn = q.n; c = q.cfg; tq = q.ts;
+            } else {
+                k = key[i];
+                nn = n[i];
+                c = cfg[i];
+            }
             uint8_t st = REFUND_INVALID;
             if (c < ncfg && nn > 0 && k != EMPTY_KEY) {
-                const int64_t t = ts[i];
+                const int64_t t = RT ? tq : ts[i];
+                if (!RT) clock = sms ? sms[i] : floor_div(t, 1000000LL);
                 const CfgDev C = cfgs[c];
                 ws = C.alg == ALG_TOKEN_BUCKET ? (int64_t)(REFUND_WS_TB | (int64_t)c) : 0;
-                code = refund_locate(k, t, sms ? sms[i] : floor_div(t, 1000000LL), C, tb, tb_mask, win, win_mask,
-                                     spill, profile, ws);
+                code = refund_locate(k, t, clock, C, tb, tb_mask, win, win_mask, spill, profile, ws);
                 st = code ? REFUND_DONE : REFUND_NOKEY;
             }
-            if (status) status[i] = st;
+            if (RT) routed_result(io, at, st, 0, 0, 0);
+            else if (status) status[i] = st;
         }
         // --- merge the wave's lanes per target, one leader each ---
         const refund_u64 lo = code ? (refund_u64)nn & 0xffffffffull : 0, hi = code ? (refund_u64)nn >> 32 : 0;
@@ -203,6 +228,51 @@ __global__ __launch_bounds__(REFUND_BLOCK) void k_refund_add(uint64_t m, const u
         }
         if (leader) refund_upsert(S, parity, code, k, ws, mylo, myhi);
     }
+    if (RT) {
+        // the merged requests past B, below the caller's bound: not executed
+        const uint64_t cnt = *io.count;
+        const uint64_t end = cnt < m_max ? cnt : m_max;
+        for (uint64_t p = bound + blockIdx.x * (uint64_t)REFUND_BLOCK + tid; p < end;
+             p += (uint64_t)gridDim.x * REFUND_BLOCK)
+            routed_result(io, f.ident ? (uint32_t)p : io.order[p], RL_DROPPED, 0, 0, 0);
+    }
+}
+
+__global__ __launch_bounds__(REFUND_BLOCK) void k_refund_add(uint64_t m, const uint64_t* __restrict__ key,
+                                                             const int64_t* __restrict__ ts,
+                                                             const int64_t* __restrict__ n,
+                                                             const uint32_t* __restrict__ cfg,
+                                                             const int64_t* __restrict__ sms,
+                                                             uint8_t* __restrict__ status,
+                                                             const CfgDev* __restrict__ cfgs, uint32_t ncfg,
+                                                             const TbEntry* tb, uint64_t tb_mask, const WinEntry* win,
+                                                             uint64_t win_mask, Spill spill, int32_t profile,
+                                                             RefundScratch S, uint32_t parity) {
+    refund_requests<false>(m, key, ts, n, cfg, sms, status, RoutedIo{}, 0, cfgs, ncfg, tb, tb_mask, win, win_mask,
+                           spill, profile, S, parity);
+}
+
+// The refund step of the routed path (rl_refund_routed_device): k_refund_add
+// on the merged batch, then k_refund_apply as it is.  The merged batch is ONE
+// refund call: all ranks' refunds of one target in the step meet in one record
+// and are applied once, whatever the merge order.  The grid is sized for
+// B = min(m_max, rl_refund_max), min(ceil(B / REFUND_BLOCK), REFUND_GRID)
+// blocks, since the host does not know the count; m = min(B, *count) is the
+// same in every thread, so the trip count stays block-uniform.  A count above
+// B: one thread raises EF_ROUTED_OVER, and the requests B <= p < min(*count,
+// m_max) get {RL_DROPPED, 0, 0, 0} -- not executed, to be resubmitted.
+// As the array form: no spin-wait; every loop is bounded by 64, MAX_PROBES,
+// the table masks, R or m_max; no CAS loop on table words; nothing is stored
+// to a state table here (k_refund_apply makes the only such store); no inline
+// assembly.  Its atomics are those of refund_upsert and the one atomicOr.
+__global__ __launch_bounds__(REFUND_BLOCK) void k_refund_add_routed(uint64_t bound, uint64_t m_max, RoutedIo io,
+                                                                    const CfgDev* __restrict__ cfgs, uint32_t ncfg,
+                                                                    const TbEntry* tb, uint64_t tb_mask,
+                                                                    const WinEntry* win, uint64_t win_mask,
+                                                                    Spill spill, int32_t profile, RefundScratch S,
+                                                                    uint32_t parity) {
+    refund_requests<true>(bound, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, io, m_max, cfgs, ncfg, tb,
+                          tb_mask, win, win_mask, spill, profile, S, parity);
 }
 
 __global__ __launch_bounds__(REFUND_BLOCK) void k_refund_apply(const CfgDev* __restrict__ cfgs, uint32_t ncfg,

@@ -310,6 +310,7 @@ _sig = {
     "rl_decide_routed_device_ev": (C.c_int, [vp, C.c_size_t] + [vp] * 7),
     "rl_peek_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
     "rl_reset_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
+    "rl_refund_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)
@@ -484,6 +485,23 @@ class Engine:
         if not event_p:
             raise ValueError("reset_routed_ev needs an event")
         self._routed_op(lib.rl_reset_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, None,
+                        event_p)
+
+    def refund_routed(self, m_max, count_p, recv_p, order_p, sms_p, res_p, stream=None, out_stream=None):
+        """rl_refund_routed_device: the refund step of the routed path -- the
+        merged batch as ONE refund call (refund()): all ranks' refunds of one
+        target are summed and applied once; result records {REFUND_DONE,
+        REFUND_NOKEY or INVALID, 0, 0, 0}, and {RL_DROPPED, 0, 0, 0} for the
+        requests past min(m_max, refund_max())"""
+        self._routed_op(lib.rl_refund_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream,
+                        out_stream, None)
+
+    def refund_routed_ev(self, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, event_p):
+        """the same with the results' completion recorded into the hipEvent_t
+        at event_p"""
+        if not event_p:
+            raise ValueError("refund_routed_ev needs an event")
+        self._routed_op(lib.rl_refund_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, None,
                         event_p)
 
     def decide_device(self, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, rem_p, retry_p, reset_p, tok_p,

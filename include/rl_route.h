@@ -39,8 +39,9 @@
  *            rl_decide_routed_device: the owner's engine reads the received
  *                               records in that order and writes 32-byte
  *                               result records at their receive index
- *            (a peek or reset step calls rl_peek_routed_device /
- *                               rl_reset_routed_device here instead; see there)
+ *            (a peek, reset or refund step calls rl_peek_routed_device /
+ *                               rl_reset_routed_device / rl_refund_routed_device
+ *                               here instead; see there)
  *            equal-split all-to-all of the result buckets back
  *   sender   rl_route_unpack    results to the caller's order
  *
@@ -207,6 +208,48 @@ int rl_peek_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, con
 int rl_reset_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
                            const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
                            void* out_stream, void* done_event);
+
+/* Refund step: the routed form of rl_refund_batch (include/rl_engine.h).  A
+ * refund step is homogeneous like the other kinds and is packed, exchanged,
+ * merged and unpacked exactly as a decide step -- the router does not change
+ * and the wire record carries no op code; the owner calls this instead of
+ * rl_decide_routed_device.  Arguments, argument checks and the stream / event
+ * behaviour are those of rl_peek_routed_device / rl_reset_routed_device.
+ *   request p   recv[order[p]] at store clock server_ms[p] (or the
+ *          RL_ORDER_IDENTITY form): a refund (key, ts, n, cfg, store clock) with
+ *          the meaning of rl_refund_batch -- ts picks the window, the store
+ *          clock decides whether the target is live.
+ *   one call    the merged batch is ONE refund call: its valid requests are
+ *          grouped by target across all source ranks, and each target with a
+ *          live contributor gets one script run with N = the saturated sum of
+ *          the contributors' n (bucket: min(capacity, tokens + N) through
+ *          tostring, last_refill and the TTL untouched; window: DEL if count <=
+ *          N, else DECRBY N).  Bucket refunds do not commute (%.14g), so the
+ *          sum is the one answer that depends neither on the thread order nor
+ *          on the merge order.
+ *   result      one rl_route_res at res[order[p]]: {RL_REFUND_DONE, 0, 0, 0}
+ *          when the request contributed, {RL_REFUND_NOKEY, 0, 0, 0} when it was
+ *          valid but found no live target (nothing is stored for it),
+ *          {RL_INVALID, 0, 0, 0} for n <= 0, an unknown cfg or RL_KEY_RESERVED.
+ *          rl_stats, the tally, the top keys and the GC budgets do not move.
+ *   bound       the kernels execute the first B = min(m_max, rl_refund_max(e))
+ *          requests of the merged batch, as one call (the engine's refund
+ *          scratch is sized for rl_refund_max).  m_max itself is limited only
+ *          by the 32-bit `order`.  If *count > B, the requests B <= p <
+ *          min(*count, m_max) get {RL_DROPPED, 0, 0, 0} -- not executed, to be
+ *          resubmitted -- and the next rl_engine_sync returns RL_EOVERFLOW, the
+ *          only sticky status the call raises.
+ * Order: as a peek or reset step -- one chain op (two kernels) on the engine's
+ * replay stream, after every engine call issued before it and before every
+ * later one; the call parity of the refund scratch is shared with
+ * rl_refund_batch_device.  Store clock: a refund step advances the router's
+ * store clock like any step (rl_route_merge, before the engine runs); a request
+ * dropped at its sender comes back RL_DROPPED and was not applied.  The first
+ * refund of an engine, routed or not, allocates the scratch (m_max == 0
+ * allocates nothing and records done_event on in_stream). */
+int rl_refund_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                            const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
+                            void* out_stream, void* done_event);
 
 /* sender: back[world * cap] (the result buckets, send layout) -> the caller's
  * order; a dropped request gets decision RL_DROPPED and zeros */
