@@ -32,4 +32,18 @@ struct TbRuns {
     uint32_t* xcnt;      // their count (a zeroed control word of the batch set)
 };
 
+// one segment: the requests of one state-table slot, [j0, j0 + len) sorted
+struct SegRec {
+    uint32_t j0;
+    uint32_t len;
+};
+
+// the segment work lists k_segments builds (rl_group.h) and the replay
+// kernels drain (rl_replay.h)
+struct SegLists {
+    SegRec* list[4];
+    uint32_t* count;      // 4 counters
+    uint32_t* claim;      // per huge segment: claimed by a replay block (zeroed per batch)
+};
+
 }  // namespace rl

@@ -6,9 +6,10 @@
 //            radix histograms of every sort pass (fused)
 //   sort     P one-sweep LSD radix passes (rl_sort.h): requests grouped by
 //            slot, arrival order kept
-//   segments one head per distinct slot -> unordered segment list
+//   segments one head per distinct slot -> unordered segment list (rl_group.h)
 //   replay   per segment, the reference's per-request semantics in arrival
-//            order, state gathered once and scattered once (rl_replay.h)
+//            order, state gathered once and scattered once (rl_replay.h;
+//            rl_tb_chain.h has the map of the decision path's headers)
 // Reference boundary replaced: go-redis Eval + Redis Lua + the Go arithmetic
 // around it (tokenbucket.go:90-193, slidingwindow.go:68-185,
 // fixedwindow.go:65-163); see include/rl_engine.h.
@@ -32,11 +33,17 @@
 #include "../../include/rl_engine.h"
 #include "../../include/rl_keyhash.h"
 #include "../../include/rl_route.h"
+#include "rl_batch.h"
 #include "rl_engine_impl.h"
 #include "rl_replay.h"
+#include "rl_group.h"   // after the replay: the code object lists the kernels in this order
 #include "rl_semantics.h"
 #include "rl_sort.h"
 #include "rl_table.h"
+#include "rl_tb_step.h"
+#include "rl_tb_window.h"
+#include "rl_tb_xdec.h"
+#include "rl_wave.h"
 
 using namespace rl;
 
@@ -400,9 +407,7 @@ constexpr int GROUP_LDS = 4096;   // LDS floor of the grouping / finish kernels 
 // carries no memset.
 constexpr uint32_t CTRL_NSEG = 0;              // [0..3] list counts (heavy TB, light, heavy window, huge TB)
                                                // [4] chain queue [5] per-thread queue [6] per-wave queue
-constexpr uint32_t CTRL_DBG = CTRL_NSEG + 8;   // [0] rounds [1] near/exact iterations [2] max rounds
-                                               // [3..6] round ends (full, stop, partial, first window)
-                                               // [8..19] timers [20] exact tiles [21] serial steps
+constexpr uint32_t CTRL_DBG = CTRL_NSEG + 8;   // the replay's debug words (DbgWord, rl_tb_stamps.h)
 constexpr uint32_t CTRL_DBGN = 88;
 constexpr uint32_t CTRL_HEAD = CTRL_DBG + CTRL_DBGN;  // words zeroed by k_probe
 constexpr uint32_t CTRL_HIST = CTRL_HEAD;             // [4][256]

@@ -2,8 +2,8 @@
 // one translation unit of the library uses.  rl_engine.hip is the decision
 // path and the engine's life cycle; rl_ops.hip Peek and Reset; rl_tables.hip
 // table maintenance and snapshots; rl_tally.hip the usage tally; rl_hot.hip
-// the top keys.  Only rl_engine.hip includes the replay (rl_replay.h): nothing
-// here does.
+// the top keys.  Only rl_engine.hip includes the grouping and the replay
+// (rl_group.h, rl_replay.h): nothing here does.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,8 +23,7 @@
 #include "rl_tally.h"
 
 namespace rl {
-struct SegRec;   // rl_replay.h
-struct UpRec;
+struct UpRec;   // rl_group.h
 }  // namespace rl
 
 constexpr int NSTAGES = 5;

@@ -1,6 +1,6 @@
 // rl_tb_xdec.h -- multi-decade ("XDEC") token-bucket windows of the chain.
-// Included by rl_tb_chain.h (after the helpers it shares with the one-decade
-// mode).
+// Shares the ring, the tile summaries and the wave helpers with the
+// one-decade mode (rl_tb_window.h).
 //
 // Why.  A hot key's stored balance is quantized to 14 significant digits
 // (tokenbucket.go:48, Lua tostring under Redis 7) and its last_refill to
@@ -41,18 +41,21 @@
 // from an exact step on its exact predecessor.
 #pragma once
 
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rl_batch.h"
+#include "rl_q14.h"
+#include "rl_semantics.h"
+#include "rl_tb_step.h"
+#include "rl_tb_window.h"
+#include "rl_wave.h"
+
 namespace rl {
 
 // the multi-decade work runs out of line in the chain kernel (see
-// ch_resolve_x in rl_tb_chain.h); RL_XDEC_OOL=0 inlines it (A/B only)
-#ifndef RL_XDEC_OOL
-#define RL_XDEC_OOL 1
-#endif
-#if RL_XDEC_OOL
+// ch_resolve_x in rl_tb_chain.h)
 #define XDEC_FN __attribute__((noinline))
-#else
-#define XDEC_FN __attribute__((always_inline)) inline
-#endif
 
 constexpr int XDEC_FMIN = -9;          // 10^(13 - F) must be an exact double: 13 - F <= 22
 constexpr int XDEC_FMAX = 8;           // decades F .. F + 4 <= 12

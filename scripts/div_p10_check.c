@@ -1,4 +1,4 @@
-/* Host check of div_p10 (csrc/rl_tb_chain.h): x / 10^k by five fma-based
+/* Host check of div_p10 (csrc/rl_tb_step.h): x / 10^k by five fma-based
  * operations with R = RN(10^-k) against IEEE division, for integer-valued x
  * below 2^47 (random, half of them in the decimal mode's [1e13, 1e14)) and
  * every k in [1, 22], plus the decade edges.  Usage: div_p10_check [samples per k]

@@ -3,7 +3,7 @@
 // (busy = 0) or next to waves running a dependent FP64 chain (busy = 1).
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include "../../distributed-rate-limiter_amd/csrc/rl_replay.h"
+#include "../../distributed-rate-limiter_amd/csrc/rl_tb_chain.h"
 using namespace rl;
 
 __global__ __launch_bounds__(512) void k_res(uint64_t* cyc, uint32_t* iters_out, int reps, int busy, int nper,
@@ -35,10 +35,12 @@ __global__ __launch_bounds__(512) void k_res(uint64_t* cyc, uint32_t* iters_out,
     double acc = 0;
     if (wave == 0) {
         uint32_t iters = 0;
+        XScale xs;   // the one-decade modes read no scale from it
+        xs.F = 0;
         const uint64_t t0 = __builtin_amdgcn_s_memtime();
         for (int r = 0; r < reps; r++) {
             s.D += 1;
-            ChOutcome o = ch_resolve<QM_DEC>(sh, s, P, R, a, runs, nullptr, iters, nullptr);
+            ChOutcome o = ch_resolve<QM_DEC>(sh, s, P, R, xs, a, runs, nullptr, iters, nullptr);
             acc += (double)o.D;
         }
         const uint64_t t1 = __builtin_amdgcn_s_memtime();

@@ -3,7 +3,8 @@
 // SIMD vs. sharing the SIMD with busy waves.
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include "../../distributed-rate-limiter_amd/csrc/rl_replay.h"
+#include "../../distributed-rate-limiter_amd/csrc/rl_tb_step.h"
+#include "../../distributed-rate-limiter_amd/csrc/rl_wave.h"
 using namespace rl;
 
 __global__ void k_lat(double* out, uint64_t* cyc, int iters, int busy) {

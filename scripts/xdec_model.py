@@ -1,4 +1,4 @@
-"""Check of the multi-decade (XDEC) window arithmetic of rl_tb_chain.h on the
+"""Check of the multi-decade (XDEC) window arithmetic of rl_tb_xdec.h on the
 hot key's exact trajectory (Python's '%.14g' / float() = Redis 7's Lua
 tostring / tonumber).
 

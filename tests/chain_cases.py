@@ -26,7 +26,7 @@ import numpy as np
 from oracle import rl_oracle_py as rpy
 from tracegen import CONFIG_SETS, NS, T0
 
-# the chain's structural constants (csrc/rl_tb_chain.h, rl_engine.hip)
+# the chain's structural constants (csrc/rl_tb_window.h, rl_engine.hip)
 CH_TILE, CH_W, CH_SERIAL, CH_NE, HUGE_MIN, HEAVY_MIN = 384, 2304, 64, 64, 4096, 32
 L = 4700                                    # one key's requests in a directed batch: two windows and 92 steps
 

@@ -1,4 +1,4 @@
-"""div_p10 (csrc/rl_tb_chain.h): the decimal step's strtod division x / 10^k as
+"""div_p10 (csrc/rl_tb_step.h): the decimal step's strtod division x / 10^k as
 five fma-based operations with RN(10^-k), checked against IEEE division on
 the host (scripts/div_p10_check.c restates the device function in C; gfx950's
 v_fma_f64 is the IEEE fused multiply-add, as the host's fma())."""

@@ -20,7 +20,7 @@ from tracegen import CONFIG_SETS, T0, random_trace
 
 pytestmark = pytest.mark.gpu
 
-UP_MAX = 1 << 21       # csrc/rl_replay.h
+UP_MAX = 1 << 21       # csrc/rl_group.h
 CONFIGS = CONFIG_SETS["mixed"]
 
 

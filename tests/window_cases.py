@@ -1,5 +1,5 @@
 """Directed traces for the fixed- and sliding-window replay (wave_win_segment,
-fw_step / sw_step, csrc/rl_tb_chain.h and csrc/rl_window.h), built by
+fw_step / sw_step, csrc/rl_replay_wave.h and csrc/rl_window.h), built by
 construction, and for every trace a predicate over the Python oracle's own
 per-request record (oracle/rl_oracle_py.py: Sim._fw, Sim._sw, Sim.db) that
 states what the trace is claimed to contain.  Nothing here calls the engine.
@@ -53,8 +53,8 @@ from oracle import rl_oracle_py as rpy
 from tracegen import NS, T0
 
 # the shortcut's structural constants
-CHUNK = 384        # requests per pass of wave_win_segment: 64 lanes * CH_K (csrc/rl_tb_chain.h)
-K = 6              # CH_K, requests per lane (csrc/rl_tb_chain.h, RL_CH_K)
+CHUNK = 384        # requests per pass of wave_win_segment: 64 lanes * CH_K (csrc/rl_tb_window.h)
+K = 6              # CH_K, requests per lane (csrc/rl_tb_window.h, RL_CH_K)
 HEAVY_MIN = 32     # rl_engine::heavy_min (csrc/rl_engine_impl.h; RL_HEAVY_MIN): segments this long take a wave
 SMALL_MAX = 4096   # SMALL_MAX (csrc/rl_engine.hip; RL_SMALL_MAX): batches up to this size run as k_small
 assert CHUNK == 64 * K
@@ -254,7 +254,7 @@ class Plan:
 
 
 def plan(case, rec):
-    """A model of wave_win_segment (csrc/rl_tb_chain.h), in plain Python: which
+    """A model of wave_win_segment (csrc/rl_replay_wave.h), in plain Python: which
     requests of the batch under test the wave takes exactly as a run's first
     ("first"), which it applies from the prefix sum ("run"), and which it
     leaves to lane 0's serial replay ("serial"), with the check that bailed
