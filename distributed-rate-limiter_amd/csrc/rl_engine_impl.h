@@ -198,6 +198,19 @@ struct rl_engine {
     uint64_t refund_calls = 0;
     hipEvent_t ev_refund = nullptr;   // rl_refund_batch_device: k_refund_apply on `chain` -> the caller's stream
 
+    // AllowAll scratch (rl_allow_all.h): one allocation made by the first call,
+    // sized for rl_allow_all_max -- the give-back amounts g, then the host
+    // form's staging of first, verdict and rollback.  The refund that reads g
+    // records ev_refund on `chain`; the next call's settle kernel, on whatever
+    // stream, waits for it before it writes g again.  It frees itself with the
+    // engine (rl_engine_destroy drains first).
+    struct AllowAllScratch {
+        void* mem = nullptr;
+        ~AllowAllScratch() {
+            if (mem) (void)hipFree(mem);
+        }
+    } allow_all;
+
     // The tally's and the top keys' kernels run on the caller's stream and read
     // the feature's own memory: the end of the last such call on each stream
     // one was enqueued on is what drain(), rl_tally_read and rl_hot_read wait

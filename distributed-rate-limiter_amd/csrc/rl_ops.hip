@@ -1,13 +1,16 @@
 // rl_ops.hip -- Peek, Reset and Refund (single, batched, routed): the
 // kernels of rl_peek.h, rl_reset.h and rl_refund.h and their C entry points.
 // Each is one chain op -- one kernel, Refund's two -- on the engine's `chain`
-// stream between two replays (chain_op, rl_engine_impl.h).
+// stream between two replays (chain_op, rl_engine_impl.h).  AllowAll
+// (rl_allow_all.h) composes a decide, its settle kernel on the caller's stream
+// and a refund.
 // A code object of its own: that of the decision kernels (rl_engine.hip) does
 // not change with it.
 #include <hip/hip_runtime.h>
 
 #include "../../include/rl_engine.h"
 #include "../../include/rl_route.h"
+#include "rl_allow_all.h"
 #include "rl_engine_impl.h"
 #include "rl_peek.h"
 #include "rl_refund.h"
@@ -71,6 +74,8 @@ static int run_routed_op(rl_engine* e, bool reset, size_t m_max, const RoutedIo&
 static int run_refund_routed(rl_engine* e, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
                              hipEvent_t done);
 
+static int allow_all_warm_up(rl_engine* e);
+
 enum RoutedKind { ROUTED_PEEK, ROUTED_RESET, ROUTED_REFUND };
 
 // the C-ABI of the routed steps: argument checks as rl_decide_routed_device_io
@@ -117,7 +122,8 @@ extern "C" int rl_refund_routed_device(rl_engine* e, size_t m_max, const uint32_
 // and nothing else), then k_peek and k_reset_batch on one request that is
 // rejected: no config is registered yet.  The staging arrays hold zeros.
 // No refund kernel is launched here, routed or not: the first refund of an
-// engine allocates its scratch, and the warm-up allocates nothing.
+// engine allocates its scratch, and the warm-up allocates nothing.  Last,
+// AllowAll's settle kernel on one member.
 int rl::ops_warm_up(rl_engine* e) {
     hipStream_t s = e->stream;
     const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
@@ -128,7 +134,9 @@ int rl::ops_warm_up(rl_engine* e) {
     const ReqArgs a{e->d_key, e->d_ts, e->d_n, e->d_cfgid, nullptr, e->d_dec, e->d_rem, e->d_retry, e->d_reset, e->d_tok};
     const int r = run_peek(e, 1, a, s, false);
     if (r != RL_OK) return r;
-    return run_reset_batch(e, 1, e->d_key, e->d_ts, e->d_cfgid, e->d_dec, s, false);
+    const int rr = run_reset_batch(e, 1, e->d_key, e->d_ts, e->d_cfgid, e->d_dec, s, false);
+    if (rr != RL_OK) return rr;
+    return allow_all_warm_up(e);
 }
 
 int rl::ops_q14_slow(rl_engine* e, unsigned long long* out) {
@@ -335,4 +343,122 @@ extern "C" int rl_refund_batch(rl_engine* e, size_t m, const uint64_t* key_id, c
     if (r != RL_OK) return r;
     HIPCHK(e, hipStreamSynchronize(s));
     return RL_OK;
+}
+
+// --- AllowAll (rl_allow_all.h) -----------------------------------------------
+
+// the engine's AllowAll scratch, allocated by the first call: g, then the
+// host form's staging of first, verdict and rollback, rl_allow_all_max each
+struct AllowAllBufs {
+    int64_t* g;
+    uint8_t *first, *verdict, *rollback;
+};
+
+static int allow_all_scratch(rl_engine* e, AllowAllBufs* out) {
+    auto& A = e->allow_all;
+    const size_t M = refund_max(e);
+    if (!A.mem && hipMalloc(&A.mem, M * (sizeof(int64_t) + 3)) != hipSuccess) {
+        A.mem = nullptr;
+        return fail(e, RL_ENOMEM, "AllowAll scratch: out of device memory");
+    }
+    out->g = (int64_t*)A.mem;
+    out->first = (uint8_t*)(out->g + M);
+    out->verdict = out->first + M;
+    out->rollback = out->verdict + M;
+    return RL_OK;
+}
+
+static int run_settle(rl_engine* e, size_t m, const uint8_t* first, const uint32_t* cfg, const int64_t* n,
+                      const uint8_t* decision, uint8_t* verdict, int64_t* g, hipStream_t s) {
+    k_allow_all_settle<<<grid_for(m, ALLOW_ALL_BLOCK, ALLOW_ALL_GRID), ALLOW_ALL_BLOCK, 0, s>>>(
+        (uint64_t)m, first, cfg, n, decision, e->d_cfg, (uint32_t)e->h_cfg.size(), verdict, g);
+    HIPCHK(e, hipGetLastError());
+    return RL_OK;
+}
+
+// One AllowAll call of 0 < m <= rl_allow_all_max members with device pointers:
+// the decide as one batch (s then sees its results), the settle kernel on s,
+// the refund of g as a chain op that always waits for s -- g is made on the
+// device, whatever RL_OPT_PIPELINE says of the caller's arrays.
+static int run_allow_all(rl_engine* e, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                         const uint32_t* cfg, const int64_t* sms, const uint8_t* first, uint8_t* decision,
+                         int64_t* remaining, int64_t* retry, int64_t* reset, double* tokens, uint8_t* verdict,
+                         uint8_t* rollback, hipStream_t s) {
+    AllowAllBufs B;
+    int r = allow_all_scratch(e, &B);
+    // the refund's scratch too, before anything is taken: a failed allocation
+    // must not leave a decide without its give-back
+    RefundScratch S;
+    if (r == RL_OK) r = refund_scratch(e, &S);
+    if (r == RL_OK) r = rl_decide_batch_device(e, m, key, ts, n, cfg, sms, decision, remaining, retry, reset, tokens, s);
+    if (r != RL_OK) return r;
+    // the previous call's refund, enqueued from any stream, may still read g:
+    // ev_refund is the end of the last refund of any kind on `chain` (a plain
+    // refund recorded since only makes the wait later)
+    if (e->refund_calls) HIPCHK(e, hipStreamWaitEvent(s, e->ev_refund, 0));
+    r = run_settle(e, m, first, cfg, n, decision, verdict, B.g, s);
+    if (r == RL_OK) r = run_refund(e, m, key, ts, B.g, cfg, sms, rollback, s, false);
+    return r;
+}
+
+// the settle kernel on one member read from the staging arrays: no config is
+// registered yet, so g = 0; the verdict and g go to staging words.  Nothing is
+// allocated.
+static int allow_all_warm_up(rl_engine* e) {
+    return run_settle(e, 1, e->d_dec, e->d_cfgid, e->d_n, (const uint8_t*)e->d_retry, (uint8_t*)e->d_tok, e->d_rem,
+                      e->stream);
+}
+
+extern "C" uint32_t rl_allow_all_max(rl_engine* e) { return e ? refund_max(e) : 0; }
+
+extern "C" int rl_allow_all_grid_cap(void) { return ALLOW_ALL_GRID * ALLOW_ALL_BLOCK; }
+
+extern "C" int rl_allow_all_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                         const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                                         const uint8_t* first, uint8_t* decision, int64_t* remaining,
+                                         int64_t* retry_after_ns, int64_t* reset_at_ns, double* tokens,
+                                         uint8_t* verdict, uint8_t* rollback, void* stream) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !first || !decision || !remaining || !retry_after_ns ||
+                     !reset_at_ns || !verdict)))
+        return RL_EINVAL;
+    if (m > refund_max(e)) return fail(e, RL_EINVAL, "AllowAll call above rl_allow_all_max");
+    if (m == 0) return RL_OK;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    return run_allow_all(e, m, key_id, ts_ns, n, cfg_id, server_ms, first, decision, remaining, retry_after_ns,
+                         reset_at_ns, tokens, verdict, rollback, s);
+}
+
+extern "C" int rl_allow_all_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                  const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                                  const uint8_t* first, uint8_t* decision, int64_t* remaining, int64_t* retry_after_ns,
+                                  int64_t* reset_at_ns, double* tokens, uint8_t* verdict, uint8_t* rollback) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !first || !decision || !remaining || !retry_after_ns ||
+                     !reset_at_ns || !verdict)))
+        return RL_EINVAL;
+    if (m > refund_max(e)) return fail(e, RL_EINVAL, "AllowAll call above rl_allow_all_max");
+    if (m == 0) return RL_OK;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    AllowAllBufs B;
+    int r = allow_all_scratch(e, &B);
+    if (r != RL_OK) return r;
+    HIPCHK(e, hipMemsetAsync(e->d_eflags, 0, 4, s));
+    // one chunk: m <= max_batch, the size of the host API's staging arrays
+    r = stage_in(e, 0, (uint32_t)m, key_id, ts_ns, n, cfg_id, server_ms, s);
+    if (r != RL_OK) return r;
+    HIPCHK(e, hipMemcpyAsync(B.first, first, m, hipMemcpyHostToDevice, s));
+    // the staged inputs arrive on s; under RL_OPT_PIPELINE the decide's
+    // grouping does not wait for s, so they are complete before it is called
+    HIPCHK(e, hipStreamSynchronize(s));
+    r = run_allow_all(e, m, e->d_key, e->d_ts, e->d_n, e->d_cfgid, server_ms ? e->d_sms : nullptr, B.first, e->d_dec,
+                      e->d_rem, e->d_retry, e->d_reset, tokens ? e->d_tok : nullptr, B.verdict,
+                      rollback ? B.rollback : nullptr, s);
+    if (r == RL_OK) r = stage_out(e, 0, (uint32_t)m, decision, remaining, retry_after_ns, reset_at_ns, tokens, s);
+    if (r != RL_OK) return r;
+    HIPCHK(e, hipMemcpyAsync(verdict, B.verdict, m, hipMemcpyDeviceToHost, s));
+    if (rollback) HIPCHK(e, hipMemcpyAsync(rollback, B.rollback, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    // the sticky device status, as rl_decide_batch returns it (a full table: RL_ENOMEM)
+    return rl_engine_sync(e);
 }

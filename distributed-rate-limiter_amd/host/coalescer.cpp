@@ -149,6 +149,7 @@ public:
             ok &= hipMemcpyAsync(a.ts, s.ts, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
             if (t.reads_n) ok &= hipMemcpyAsync(a.n, s.n, 8 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
             ok &= hipMemcpyAsync(a.cfg, s.cfg, 4 * m, hipMemcpyHostToDevice, cs_) == hipSuccess;
+            if (t.grouped) ok &= hipMemcpyAsync(a.head, s.head, m, hipMemcpyHostToDevice, cs_) == hipSuccess;
             ok &= hipEventRecord(d.ev_in, cs_) == hipSuccess;
             ok &= await_event(d.ev_in) == hipSuccess;
             if (!ok) return RL_EDEVICE;
@@ -164,6 +165,7 @@ public:
                 ok &= hipMemcpyAsync(s.retry, a.retry, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
                 ok &= hipMemcpyAsync(s.reset, a.reset, 8 * m, hipMemcpyDeviceToHost, os_) == hipSuccess;
             }
+            if (t.grouped) ok &= hipMemcpyAsync(s.verdict, a.verdict, m, hipMemcpyDeviceToHost, os_) == hipSuccess;
         }
         ok &= hipEventRecord(d.ev, os_) == hipSuccess;
         return ok ? RL_OK : RL_EDEVICE;
@@ -172,7 +174,8 @@ public:
     // slot's completion event) waits for it.  A reset or a refund is one or
     // two kernels on the engine's replay stream between two batches.  Behind
     // a successful decide, the tally and then the top keys count the batch on
-    // os_, on the arrays the decide used.
+    // os_, on the arrays the decide used; behind an AllowAll call they count
+    // its members the same way, with the members' own decisions.
     int engine_call(Op op, size_t m, const Arrays& a) {
         switch (op) {
             case OP_REQ: {
@@ -187,6 +190,13 @@ public:
                                             os_);
             case OP_RESET: return rl_reset_batch_device(e_, m, a.key, a.ts, a.cfg, a.dec, os_);
             case OP_REFUND: return rl_refund_batch_device(e_, m, a.key, a.ts, a.n, a.cfg, nullptr, a.dec, os_);
+            case OP_ALLOW_ALL: {
+                int rc = rl_allow_all_batch_device(e_, m, a.key, a.ts, a.n, a.cfg, nullptr, a.head, a.dec, a.rem, a.retry,
+                                                   a.reset, nullptr, a.verdict, nullptr, os_);
+                if (rc == RL_OK && tally_) rc = rl_tally_batch_device(e_, m, a.key, a.cfg, a.n, a.dec, os_);
+                if (rc == RL_OK && hot_) rc = rl_hot_batch_device(e_, m, a.key, a.cfg, a.n, a.dec, os_);
+                return rc;
+            }
             default: return RL_EINVAL;
         }
     }
@@ -491,6 +501,14 @@ public:
             case OP_PEEK:
                 return b_.peek ? b_.peek(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.rem, s.retry, s.reset) : RL_EINVAL;
             case OP_REFUND: return b_.refund ? b_.refund(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec) : RL_EINVAL;
+            case OP_ALLOW_ALL: {
+                if (!b_.allow_all) return RL_EINVAL;
+                const int rc = b_.allow_all(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.head, s.dec, s.rem, s.retry, s.reset,
+                                            s.verdict);
+                if (rc == RL_OK && tally_on_) tally_.add(s.m, s.key, s.cfg, s.n, s.dec);
+                if (rc == RL_OK && hot_on_) hot_.add(s.m, s.key, s.cfg, s.n, s.dec);
+                return rc;
+            }
             case OP_RESET: return reset_batch(s);
             default: return RL_EINVAL;
         }
@@ -598,10 +616,11 @@ void Coalescer::SetNotify(NotifyFn fn, void* user) {
 }
 
 int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
-                      uint64_t* ticket, int64_t deadline, void* tag, Op op) {
+                      uint64_t* ticket, int64_t deadline, void* tag, Op op, const uint8_t* first) {
     if (op >= OP_COUNT || !OPS[op].batched) return RL_EINVAL;
     const OpTraits& t = OPS[op];
-    if (!ticket || (m && (!key || !ts || !cfg || (!n && t.reads_n))) || deadline < 0) return RL_EINVAL;
+    if (!ticket || (m && (!key || !ts || !cfg || (!n && t.reads_n) || (!first && t.grouped))) || deadline < 0)
+        return RL_EINVAL;
     // a submission that is not split is one launch (a refund: the engine's sum rule)
     if (!t.splits && m > o_.max_batch) return RL_EINVAL;
     Sub* s = get_sub(m);
@@ -613,6 +632,7 @@ int Coalescer::Submit(size_t m, const uint64_t* key, const int64_t* ts, const in
     memcpy(s->ts, ts, 8 * m);
     if (n) memcpy(s->n, n, 8 * m);
     memcpy(s->cfg, cfg, 4 * m);
+    if (t.grouped) memcpy(s->head, first, m);
     return enqueue(s, m, ticket);
 }
 
@@ -691,7 +711,7 @@ int Coalescer::Cancel(uint64_t ticket) {
 }
 
 int Coalescer::Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* rem, int64_t* retry,
-                    int64_t* reset, int64_t* done_ns, rl_table_info* info) {
+                    int64_t* reset, int64_t* done_ns, rl_table_info* info, uint8_t* verdict) {
     std::unique_lock<std::mutex> lk(mu_);
     auto it = subs_.find(ticket);
     if (it == subs_.end()) return RL_EINVAL;
@@ -740,6 +760,7 @@ int Coalescer::Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* 
         if (retry) memcpy(retry, s->retry, 8 * m);
         if (reset) memcpy(reset, s->reset, 8 * m);
     }
+    if (OPS[s->op].grouped && verdict) memcpy(verdict, s->verdict, m);
     if (info) *info = s->info;
     if (done_ns) *done_ns = s->done_ns;
     int st = s->status;
@@ -954,7 +975,8 @@ void Coalescer::submitter() {
             // the queue head is one launch, enqueued between the batches
             // around it; a peek submission is launched on its own, and so is
             // a refund submission (one engine call: the engine sums the
-            // refunds of a call per target)
+            // refunds of a call per target) and an AllowAll submission (its
+            // groups' transient takes must not depend on the queue's timing)
             if (sub->op != f->op || (!t.merges && sub != f)) break;
             // its context ended before (the rest of) it was sent: that part is never applied
             if (sub->taken < sub->m && (sub->cancelled || (sub->deadline && sub->deadline <= now)))
@@ -983,6 +1005,7 @@ void Coalescer::submitter() {
             memcpy(s.ts + p.at, p.sub->ts + p.off, 8 * p.count);
             if (t.reads_n) memcpy(s.n + p.at, p.sub->n + p.off, 8 * p.count);
             memcpy(s.cfg + p.at, p.sub->cfg + p.off, 4 * p.count);
+            if (t.grouped) memcpy(s.head + p.at, p.sub->head + p.off, p.count);
         }
         s.m = m;
         // only a decision inserts: the others have no part in the automatic GC's budgets
@@ -1024,6 +1047,7 @@ void Coalescer::completer() {
                 memcpy(p.sub->rem + p.off, s.rem + p.at, 8 * p.count);
                 memcpy(p.sub->retry + p.off, s.retry + p.at, 8 * p.count);
                 memcpy(p.sub->reset + p.off, s.reset + p.at, 8 * p.count);
+                if (t.grouped) memcpy(p.sub->verdict + p.off, s.verdict + p.at, p.count);
             }
         } else {
             // a status: meaningful only when the launch succeeded; RL_RESET_DONE
@@ -1034,11 +1058,16 @@ void Coalescer::completer() {
                 for (size_t i = 0; i < s.m; i++) completed += s.dec[i] == RL_RESET_DONE;
             }
         }
+        // the groups of a launch that ran: never merged, so member 0 starts one
+        uint64_t groups = 0;
+        if (t.grouped && st == RL_OK)
+            for (size_t i = 0; i < s.m; i++) groups += i == 0 || s.head[i] != 0;
         const int64_t now = steady_ns();
         bool wake;
         {
             std::lock_guard<std::mutex> g(mu_);
             wake = sub_idle_;
+            st_.allow_all_groups += groups;
             launched_.pop_front();
             inflight_--;
             if (trace_cap_) {
@@ -1107,11 +1136,12 @@ extern "C" int rl_coalescer_create(rl_engine* e, const rl_coalescer_opts* opts, 
 
 extern "C" int rl_coalescer_create_with_host_backend(const rl_coalescer_backend* be, const rl_coalescer_opts* opts,
                                                      rl_coalescer** out) {
-    // a caller compiled before `peek` / `reset_batch` / `refund` were added passes the shorter struct
+    // a caller compiled before `peek` / `reset_batch` / `refund` / `allow_all` were added passes the shorter struct
     if (!be || !out ||
         (be->struct_size != sizeof(rl_coalescer_backend) && be->struct_size != offsetof(rl_coalescer_backend, peek) &&
          be->struct_size != offsetof(rl_coalescer_backend, reset_batch) &&
-         be->struct_size != offsetof(rl_coalescer_backend, refund)))
+         be->struct_size != offsetof(rl_coalescer_backend, refund) &&
+         be->struct_size != offsetof(rl_coalescer_backend, allow_all)))
         return RL_EINVAL;
     rl_coalescer_backend b{};
     memcpy(&b, be, be->struct_size);
@@ -1127,7 +1157,8 @@ extern "C" int rl_coalescer_create_with_backend(rl_batch_fn fn, void* user, cons
 
 extern "C" int rl_coalescer_create_with_backends(rl_batch_fn fn, rl_reset_fn reset_fn, void* user,
                                                  const rl_coalescer_opts* opts, rl_coalescer** out) {
-    rl_coalescer_backend b{sizeof(rl_coalescer_backend), fn, reset_fn, nullptr, nullptr, user, nullptr, nullptr, nullptr};
+    rl_coalescer_backend b{sizeof(rl_coalescer_backend), fn, reset_fn, nullptr, nullptr, user, nullptr, nullptr, nullptr,
+                           nullptr};
     return rl_coalescer_create_with_host_backend(&b, opts, out);
 }
 
@@ -1210,6 +1241,19 @@ extern "C" int rl_coalescer_refund(rl_coalescer* c, size_t m, const uint64_t* ke
     int rc = c->c->Submit(m, key_id, ts_ns, n, cfg_id, &t, 0, nullptr, rlc::OP_REFUND);
     if (rc != RL_OK) return rc;
     return c->c->Wait(t, -1, status, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rl_coalescer_allow_all(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                      const int64_t* n, const uint32_t* cfg_id, const uint8_t* first,
+                                      int64_t deadline_ns, uint8_t* decision, int64_t* remaining,
+                                      int64_t* retry_after_ns, int64_t* reset_at_ns, uint8_t* verdict) {
+    if (!c) return RL_EINVAL;
+    // one submission is one launch: a larger one is not split (the refund's sum rule)
+    if (m > c->c->MaxBatch()) return RL_EINVAL;
+    uint64_t t;
+    int rc = c->c->Submit(m, key_id, ts_ns, n, cfg_id, &t, deadline_ns, nullptr, rlc::OP_ALLOW_ALL, first);
+    if (rc != RL_OK) return rc;
+    return c->c->Wait(t, -1, decision, remaining, retry_after_ns, reset_at_ns, nullptr, nullptr, verdict);
 }
 
 extern "C" int rl_coalescer_peek(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,

@@ -26,7 +26,7 @@
 
 namespace rlc {
 
-enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_REFUND, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT, OP_COUNT };
+enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_REFUND, OP_ALLOW_ALL, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT, OP_COUNT };
 
 // What the queue, the launch and the counters do with a submission of each
 // operation: stated once here and read everywhere else (a `switch (op)` stays
@@ -52,21 +52,25 @@ struct OpTraits {
     StatField launches;    // its own launch counter, if any
     StatField completed;   // at completion: += m (results), or += the statuses that say done
     bool keeps_gc_count;   // a table operation that touches no table: the automatic GC's count still holds
+    // its requests come in groups: `first` goes in with them, `verdict` comes
+    // back with the results, and the groups launched count in allow_all_groups
+    bool grouped;
 };
 constexpr StatField NO_STAT = nullptr;
 using St = rl_coalescer_stats;
 constexpr OpTraits OPS[OP_COUNT] = {
-    //             batched reads_n results merges splits q_cap  decides batch  max    launches              completed      keeps_gc
-    /* REQ      */ {true,  true,   true,   true,  true,  true,  true,   true,  true,  NO_STAT,              &St::decided,  false},
-    /* RESET    */ {true,  false,  false,  true,  true,  false, false,  true,  false, &St::reset_launches,  &St::resets,   false},
-    /* PEEK     */ {true,  true,   true,   false, true,  true,  false,  false, false, NO_STAT,              &St::peeked,   false},
-    /* REFUND   */ {true,  true,   false,  false, false, true,  false,  false, false, &St::refund_launches, &St::refunds,  false},
-    /* INFO     */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       false},
-    /* GC       */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       false},
-    /* SNAPSHOT */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       false},
-    /* RESTORE  */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       false},
-    /* TALLY    */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       true},
-    /* HOT      */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,              NO_STAT,       true},
+    //              batched reads_n results merges splits q_cap  decides batch  max    launches                 completed      keeps_gc grouped
+    /* REQ       */ {true,  true,   true,   true,  true,  true,  true,   true,  true,  NO_STAT,                 &St::decided,  false,   false},
+    /* RESET     */ {true,  false,  false,  true,  true,  false, false,  true,  false, &St::reset_launches,     &St::resets,   false,   false},
+    /* PEEK      */ {true,  true,   true,   false, true,  true,  false,  false, false, NO_STAT,                 &St::peeked,   false,   false},
+    /* REFUND    */ {true,  true,   false,  false, false, true,  false,  false, false, &St::refund_launches,    &St::refunds,  false,   false},
+    /* ALLOW_ALL */ {true,  true,   true,   false, false, true,  true,   false, false, &St::allow_all_launches, &St::decided,  false,   true},
+    /* INFO      */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       false,   false},
+    /* GC        */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       false,   false},
+    /* SNAPSHOT  */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       false,   false},
+    /* RESTORE   */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       false,   false},
+    /* TALLY     */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       true,    false},
+    /* HOT       */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       true,    false},
 };
 
 // the SoA arrays of one block of requests and results
@@ -79,12 +83,16 @@ struct Arrays {
     int64_t* rem = nullptr;
     int64_t* retry = nullptr;
     int64_t* reset = nullptr;
+    uint8_t* head = nullptr;      // a grouped operation's group heads, `first` of the C-ABI (in) ...
+    uint8_t* verdict = nullptr;   // ... and its per-member group verdict (out)
 };
 // The one layout of such a block -- a slot's pinned host block, its device
 // block, a host backend's heap block, a submission's buffer --, by capacity:
-// key ts n | cfg | rem retry reset | dec, the result area 64-byte aligned (the
-// device path needs that).  block_bytes(cap) holds it.
-constexpr size_t block_bytes(size_t cap) { return cap * 61 + 64; }
+// key ts n | cfg | rem retry reset | dec | head | verdict, the result area
+// 64-byte aligned (the device path needs that).  block_bytes(cap) holds it.
+// head and verdict, which only a grouped operation uses, come last: the
+// offsets of the others, and the plain path's copies, do not depend on them.
+constexpr size_t block_bytes(size_t cap) { return cap * 63 + 64; }
 inline void carve(uint8_t* p, size_t cap, Arrays& a) {
     a.key = reinterpret_cast<uint64_t*>(p);
     a.ts = reinterpret_cast<int64_t*>(p + 8 * cap);
@@ -95,6 +103,8 @@ inline void carve(uint8_t* p, size_t cap, Arrays& a) {
     a.retry = reinterpret_cast<int64_t*>(q + 8 * cap);
     a.reset = reinterpret_cast<int64_t*>(q + 16 * cap);
     a.dec = q + 24 * cap;
+    a.head = q + 25 * cap;
+    a.verdict = q + 26 * cap;
 }
 
 // one launch's staging buffers (host side; pinned for the GPU backend)
@@ -179,7 +189,9 @@ public:
     // wait(slot).  OP_REQ: decisions (rl_decide_batch_device); OP_PEEK:
     // read-only queries (rl_peek_batch_device); OP_RESET: resets (key, ts, cfg;
     // rl_reset_batch_device) and OP_REFUND: one refund call
-    // (rl_refund_batch_device), both with the per-request status into s.dec
+    // (rl_refund_batch_device), both with the per-request status into s.dec;
+    // OP_ALLOW_ALL: one AllowAll call (rl_allow_all_batch_device), s.head in,
+    // s.verdict out beside the decide's results
     virtual int launch(int slot, Slot& s) = 0;
     virtual int wait(int slot, Slot& s) = 0;     // until launch `slot` completed
     // synchronous table operations (the GPU engine drains its batches first)
@@ -255,9 +267,13 @@ public:
     // decided --, or OP_RESET: m resets (n is not read), merged with the reset
     // submissions next to it in the queue into one launch; Wait's `dec`
     // receives their status; or OP_REFUND: one refund call of m <= max_batch
-    // requests, launched whole and on its own; Wait's `dec` receives the status
+    // requests, launched whole and on its own; Wait's `dec` receives the status;
+    // or OP_ALLOW_ALL: one AllowAll call of m <= max_batch members in the
+    // groups `first` marks, launched whole and on its own, counted like
+    // requests; Wait's `verdict` receives each member's group verdict
     int Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
-               uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr, Op op = OP_REQ);
+               uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr, Op op = OP_REQ,
+               const uint8_t* first = nullptr);
     // one table operation (an op without OPS[op].batched: table count, table
     // GC, snapshot, restore, tally read, top-keys read), queued in sequence
     // order; never refused by a full queue
@@ -281,7 +297,7 @@ public:
     // done_ns (optional): steady-clock completion time of the submission;
     // info (optional): an OP_INFO / OP_GC result
     int Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* rem, int64_t* retry, int64_t* reset,
-             int64_t* done_ns = nullptr, rl_table_info* info = nullptr);
+             int64_t* done_ns = nullptr, rl_table_info* info = nullptr, uint8_t* verdict = nullptr);
     rl_coalescer_stats Stats();
     void Shutdown();
     // the trace ring, oldest first (empty unless RL_COALESCER_TRACE is set)

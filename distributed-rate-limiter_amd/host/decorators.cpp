@@ -79,6 +79,27 @@ Error MetricsDecorator::RefundMany(const Context& ctx, const std::vector<RefundR
     return e;
 }
 
+void MetricsDecorator::ObserveAllowAll(const AllowAllEvent& ev) {
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        allow_all_used_ = true;
+        allow_alls_[ev.error.empty() && ev.allowed ? 1 : 0]++;
+        const uint64_t u = ev.rolled_back_units;
+        rolled_back_units_ = rolled_back_units_ + u < rolled_back_units_ ? UINT64_MAX : rolled_back_units_ + u;
+    }
+    inner_->ObserveAllowAll(ev);
+}
+
+uint64_t MetricsDecorator::AllowAlls(bool allowed) const {
+    std::lock_guard<std::mutex> g(mu_);
+    return allow_alls_[allowed ? 1 : 0];
+}
+
+uint64_t MetricsDecorator::RolledBackUnits() const {
+    std::lock_guard<std::mutex> g(mu_);
+    return rolled_back_units_;
+}
+
 uint64_t MetricsDecorator::Refunds(bool applied) const {
     std::lock_guard<std::mutex> g(mu_);
     return refunds_[applied ? 1 : 0];
@@ -139,6 +160,21 @@ std::string MetricsDecorator::Expose() const {
                  (unsigned long long)refunded_units_);
         s += line;
     }
+    if (allow_all_used_) {
+        s += "# HELP rate_limiter_allow_all_total All-or-nothing group checks this limiter was a member of.\n"
+             "# TYPE rate_limiter_allow_all_total counter\n";
+        for (int a = 0; a < 2; a++) {
+            snprintf(line, sizeof line, "rate_limiter_allow_all_total{allowed=\"%s\"} %llu\n", a ? "true" : "false",
+                     (unsigned long long)allow_alls_[a]);
+            s += line;
+        }
+        s += "# HELP rate_limiter_allow_all_rolled_back_units_total Units taken by this limiter in a failed group "
+             "and given back.\n"
+             "# TYPE rate_limiter_allow_all_rolled_back_units_total counter\n";
+        snprintf(line, sizeof line, "rate_limiter_allow_all_rolled_back_units_total{algorithm=\"%s\"} %llu\n",
+                 alg.c_str(), (unsigned long long)rolled_back_units_);
+        s += line;
+    }
     return s;
 }
 
@@ -181,6 +217,18 @@ Error LoggingDecorator::ResetManyAt(const Context& ctx, const std::vector<std::s
     Error e = inner_->ResetManyAt(ctx, keys, t);
     if (e) sink_(LogLevel::Error, "rate limiter reset error", {{"keys", std::to_string(keys.size())}, {"error", e.msg}});
     return e;
+}
+
+void LoggingDecorator::ObserveAllowAll(const AllowAllEvent& ev) {
+    if (!ev.error.empty())
+        sink_(LogLevel::Error, "rate limiter allow-all error",
+              {{"key", ev.key}, {"members", std::to_string(ev.members)}, {"error", ev.error}});
+    else if (!ev.allowed)
+        sink_(LogLevel::Debug, "allow-all denied",
+              {{"key", ev.key}, {"n", std::to_string(ev.n)}, {"member", std::to_string(ev.index)},
+               {"denied_by", std::to_string(ev.denied_by)},
+               {"rolled_back_units", std::to_string(ev.rolled_back_units)}});
+    inner_->ObserveAllowAll(ev);
 }
 
 Error LoggingDecorator::RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,

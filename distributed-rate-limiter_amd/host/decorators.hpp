@@ -50,6 +50,14 @@ public:
     void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                     std::vector<BatchOutcome>* out) override;
     const Config& config() const override { return inner_->config(); }
+    bool AllowAllMemberOf(const std::string& key, int64_t now_ns, bool intern, AllowAllMember* m) override {
+        return inner_->AllowAllMemberOf(key, now_ns, intern, m);
+    }
+    // groups this limiter was a member of, by the group's outcome, and the
+    // units of its own takes that were given back
+    void ObserveAllowAll(const AllowAllEvent& ev) override;
+    uint64_t AllowAlls(bool allowed) const;
+    uint64_t RolledBackUnits() const;
     // refunds counted so far: [0] without live state, [1] applied; units of the applied ones
     uint64_t Refunds(bool applied) const;
     uint64_t RefundedUnits() const;
@@ -73,6 +81,9 @@ private:
     uint64_t observations_ = 0;
     uint64_t refunds_[2] = {0, 0};
     uint64_t refunded_units_ = 0;       // saturates
+    uint64_t allow_alls_[2] = {0, 0};   // [0] denied or failed, [1] allowed
+    uint64_t rolled_back_units_ = 0;    // saturates
+    bool allow_all_used_ = false;
 };
 
 enum class LogLevel { Debug = 0, Info = 1, Warn = 2, Error = 3 };
@@ -94,6 +105,11 @@ public:
     Error PeekN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, Result* out) override {
         return inner_->PeekN(ctx, key, n, now_ns, out);
     }
+    bool AllowAllMemberOf(const std::string& key, int64_t now_ns, bool intern, AllowAllMember* m) override {
+        return inner_->AllowAllMemberOf(key, now_ns, intern, m);
+    }
+    // "allow-all denied" at Debug per denied group, "rate limiter allow-all error" at Error per failed call
+    void ObserveAllowAll(const AllowAllEvent& ev) override;
     // "quota refunded" at Debug per request, "rate limiter refund error" at Error per failed call
     Error RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
                      std::vector<uint8_t>* applied) override;

@@ -228,8 +228,10 @@ struct Conn;
 
 // K_PEEK: a read-only AllowN (rl_coalescer_peek); K_RESET_BATCH: many resets, one coalescer submission;
 // K_USAGE: RateLimiterMetrics.Usage, one rl_coalescer_tally; K_TOPKEYS: RateLimiterTopKeys.TopKeys, one
-// rl_coalescer_hot; K_REFUND / K_REFUND_BATCH: RateLimiterRefund, one refund submission (rl_coalescer_refund)
-enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE, K_TOPKEYS, K_REFUND, K_REFUND_BATCH, K_COUNT };
+// rl_coalescer_hot; K_REFUND / K_REFUND_BATCH: RateLimiterRefund, one refund submission (rl_coalescer_refund);
+// K_ALLOW_ALL / K_ALLOW_ALL_BATCH: RateLimiterMulti, one AllowAll submission (rl_coalescer_allow_all)
+enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE, K_TOPKEYS, K_REFUND, K_REFUND_BATCH,
+                      K_ALLOW_ALL, K_ALLOW_ALL_BATCH, K_COUNT };
 
 // What each kind of RPC asks of the coalescer and how it reports, stated once.
 struct KindTraits {
@@ -267,6 +269,10 @@ constexpr KindTraits KINDS[K_COUNT] = {
                           nullptr, false, false, false},
     /* K_REFUND_BATCH */ {rlc::OP_REFUND, false, false, "failed to refund rate limit: ", nullptr,
                           "bad RefundBatchRequest", true, true, false},
+    /* K_ALLOW_ALL    */ {rlc::OP_ALLOW_ALL, true, true, "failed to check rate limit: ", nullptr,
+                          "bad AllowAllRequest", true, false, false},
+    /* K_ALLOW_ALL_BATCH */ {rlc::OP_ALLOW_ALL, true, true, "failed to check rate limit: ", nullptr,
+                          "bad AllowAllBatchRequest", true, false, false},
 };
 // a queued read that writes into buffers its Rpc owns: not cancelled when its
 // client goes away, but detached and left to finish
@@ -307,6 +313,14 @@ struct BatchItem {
     uint64_t id = 0;           // Rpc.named: its key id
 };
 
+// one request of a RateLimiterMulti RPC: its checks are `checks` entries of
+// Rpc.items (none when it cannot run: err says why, and `results` results
+// carry it)
+struct GroupItem {
+    size_t checks = 0, results = 0;
+    std::string err;
+};
+
 struct Rpc {
     Conn* conn;
     int32_t sid;
@@ -319,6 +333,7 @@ struct Rpc {
     std::string key;           // K_ALLOW, named: the key's name
     uint64_t id = 0;           // K_ALLOW, named: its key id
     bool named = false;        // the names were kept (Server::keep_names when the RPC came in)
+    std::vector<GroupItem> groups;     // K_ALLOW_ALL, K_ALLOW_ALL_BATCH
     std::unique_ptr<UsageBuf> usage;   // K_USAGE
     std::unique_ptr<HotBuf> hot;       // K_TOPKEYS
 };
@@ -643,6 +658,7 @@ void put_topkeys(std::string& msg, Server* s, const HotBuf& h) {
 struct Results {
     const uint8_t* dec = nullptr;
     const int64_t *rem = nullptr, *retry = nullptr, *reset = nullptr;
+    const uint8_t* verdict = nullptr;   // an AllowAll submission's group verdicts
     // a reset's or a refund's status (RL_RESET_DONE and RL_REFUND_DONE are one code)
     bool done(size_t j) const { return dec && dec[j] == RL_RESET_DONE; }
 };
@@ -696,6 +712,50 @@ void finish_rpc(Io* io, Rpc& rpc, int rc, const Results& r = {}) {
             if (failed()) return;
             put_int(msg, 1, r.done(0) ? 1 : 0);   // RefundResponse.applied = 1
             break;
+        case K_ALLOW_ALL:
+        case K_ALLOW_ALL_BATCH: {
+            // AllowAllResponse {allowed = 1, results = 2, denied_by = 3, rolled_back = 4 (packed)} per request;
+            // the batch response holds them as field 1 (python/rl_server.py _allow_all)
+            size_t at = 0, item = 0;
+            std::string one, res;
+            for (const GroupItem& g : rpc.groups) {
+                one.clear();
+                if (!g.err.empty()) {
+                    if (rpc.kind == K_ALLOW_ALL) return respond_err(c, st, GRPC_INVALID_ARGUMENT, g.err);
+                    Result e;
+                    e.error = g.err;
+                    for (size_t j = 0; j < g.results; j++) {
+                        res.clear();
+                        put_allow_response(res, e);
+                        put_msg(one, 2, res);
+                    }
+                    put_int(one, 3, -1);
+                } else {
+                    int64_t by = -1;
+                    std::string rolled, all;
+                    for (size_t j = 0; j < g.checks; j++, at++, item++) {
+                        const Limiter* lim = rpc.items[item].lim;
+                        const uint8_t d = r.dec ? r.dec[at] : 0;
+                        const Outcome o = decide_outcome(lim, rpc.t, rc, d, r.rem ? r.rem[at] : 0,
+                                                         r.retry ? r.retry[at] : 0, r.reset ? r.reset[at] : 0);
+                        if (o.code != GRPC_OK && rpc.kind == K_ALLOW_ALL) return respond_err(c, st, o.code, o.r.error);
+                        if (!o.r.allowed && by < 0) by = (int64_t)j;
+                        res.clear();
+                        put_allow_response(res, o.r);
+                        put_msg(all, 2, res);
+                        const bool took = d == RL_ALLOWED || (d == RL_DENIED && lim->alg != rl::ALG_TOKEN_BUCKET);
+                        rolled.push_back(rc == RL_OK && r.verdict && r.verdict[at] != RL_ALLOWED && took ? 1 : 0);
+                    }
+                    put_int(one, 1, by < 0 ? 1 : 0);
+                    one += all;
+                    put_int(one, 3, by);
+                    put_bytes(one, 4, rolled);
+                }
+                if (rpc.kind == K_ALLOW_ALL) msg = one;
+                else put_msg(msg, 1, one);
+            }
+            break;
+        }
         case K_ALLOW:
         case K_PEEK: {
             const Outcome o = allow_outcome(io, rpc, rpc.lim, rpc.id, rpc.key, rc, r, 0);
@@ -747,11 +807,12 @@ void collect(Io* io, uint64_t ticket) {
     if (it == io->rpcs.end()) return;   // already collected (a deadline, a cancel)
     Rpc& rpc = it->second;
     const size_t m = rpc.m;
-    std::vector<uint8_t> dec(m);
+    std::vector<uint8_t> dec(m), verdict(m);
     std::vector<int64_t> rem(m), retry(m), reset(m);
-    const int rc = io->srv->co->Wait(ticket, 0, dec.data(), rem.data(), retry.data(), reset.data());
+    const int rc = io->srv->co->Wait(ticket, 0, dec.data(), rem.data(), retry.data(), reset.data(), nullptr, nullptr,
+                                     verdict.data());
     if (rc == RL_ETIMEOUT) return;      // not done yet (a spurious wake)
-    finish_rpc(io, rpc, rc, Results{dec.data(), rem.data(), retry.data(), reset.data()});
+    finish_rpc(io, rpc, rc, Results{dec.data(), rem.data(), retry.data(), reset.data(), verdict.data()});
     io->rpcs.erase(it);
 }
 
@@ -769,7 +830,7 @@ void await_ticket(Io* io, Stream* st, Rpc&& rpc, int rc, uint64_t ticket) {
 // one coalescer submission per RPC, completed through the ticket's
 // notification: the event loop never blocks
 void submit_rpc(Io* io, Stream* st, Rpc&& rpc, const uint64_t* key, const int64_t* ts, const int64_t* n,
-                const uint32_t* cfg) {
+                const uint32_t* cfg, const uint8_t* first = nullptr) {
     Server* s = io->srv;
     const KindTraits& k = KINDS[rpc.kind];
     rpc.deadline = st->timeout_ns >= 0 && st->timeout_ns < NO_DEADLINE_NS
@@ -777,7 +838,7 @@ void submit_rpc(Io* io, Stream* st, Rpc&& rpc, const uint64_t* key, const int64_
                        : 0;
     uint64_t ticket = 0;
     const int rc = s->co->Submit(rpc.m, key, ts, rlc::OPS[k.op].reads_n ? n : nullptr, cfg, &ticket,
-                                 k.deadline ? rpc.deadline : 0, io, k.op);
+                                 k.deadline ? rpc.deadline : 0, io, k.op, first);
     if (k.decides) s->n_dec += rpc.m;
     await_ticket(io, st, std::move(rpc), rc, ticket);
 }
@@ -846,6 +907,78 @@ void dispatch_batch(Conn* c, Stream* st, std::string_view msg, Kind kind) {
     submit_rpc(io, st, std::move(rpc), key.data(), ts.data(), n.data(), cfg.data());
 }
 
+// RateLimiterMulti: an AllowAllRequest (repeated AllowNRequest checks = 1), or
+// a message of repeated AllowAllRequest (field 1), is one AllowAll submission
+// of the groups that can run; a request that cannot keeps its error
+void dispatch_allow_all(Conn* c, Stream* st, std::string_view msg, Kind kind) {
+    Io* io = c->io;
+    Server* s = io->srv;
+    const KindTraits& k = KINDS[kind];
+    Rpc rpc{c, st->id, kind, s->now(), 0, nullptr, {}, 0};
+    std::vector<uint64_t> key;
+    std::vector<int64_t> ts, n;
+    std::vector<uint32_t> cfg;
+    std::vector<uint8_t> first;
+    bool ok = true;
+    const auto group = [&](std::string_view body) {
+        std::vector<ReqMsg> checks;
+        Pb pb{(const uint8_t*)body.data(), (const uint8_t*)body.data() + body.size()};
+        while (pb.more()) {
+            const uint64_t tag = pb.varint();
+            if ((tag >> 3) != 1 || (tag & 7) != 2) {
+                pb.skip((uint32_t)(tag & 7));
+                continue;
+            }
+            ReqMsg r;
+            if (!parse_req(pb.bytes(), &r) || !pb.ok) return false;
+            checks.push_back(r);
+        }
+        if (!pb.ok) return false;
+        GroupItem g;
+        if (checks.empty() || checks.size() > RL_ALLOW_ALL_MAX_GROUP)
+            g.err = "checks: need 1 to 16, got " + std::to_string(checks.size());
+        for (size_t j = 0; j < checks.size() && g.err.empty(); j++) {
+            if (!s->find(checks[j].limiter)) g.err = "unknown limiter " + py_repr(checks[j].limiter);
+            else if (checks[j].n <= 0) g.err = ERR_INVALID_N;
+        }
+        if (!g.err.empty()) {
+            g.results = std::max<size_t>(1, checks.size());
+        } else {
+            g.checks = checks.size();
+            for (size_t j = 0; j < checks.size(); j++) {
+                const Limiter* lim = s->find(checks[j].limiter);
+                key.push_back(s->key_id(lim, checks[j].key));
+                ts.push_back(rpc.t);
+                n.push_back(checks[j].n);
+                cfg.push_back(lim->cfg);
+                first.push_back(j == 0 ? 1 : 0);
+                rpc.items.push_back(BatchItem{lim, 0, {}});
+            }
+        }
+        rpc.groups.push_back(std::move(g));
+        return true;
+    };
+    if (kind == K_ALLOW_ALL) {
+        ok = group(msg);
+    } else {
+        Pb pb{(const uint8_t*)msg.data(), (const uint8_t*)msg.data() + msg.size()};
+        while (ok && pb.more()) {
+            const uint64_t tag = pb.varint();
+            if ((tag >> 3) != 1 || (tag & 7) != 2) {
+                pb.skip((uint32_t)(tag & 7));
+                continue;
+            }
+            const std::string_view body = pb.bytes();
+            ok = pb.ok && group(body);
+        }
+        ok = ok && pb.ok;
+    }
+    if (!ok) return respond_err(c, st, GRPC_INTERNAL, k.bad);
+    rpc.m = key.size();
+    if (rpc.m == 0) return finish_rpc(io, rpc, RL_OK);
+    submit_rpc(io, st, std::move(rpc), key.data(), ts.data(), n.data(), cfg.data(), first.data());
+}
+
 void dispatch(Conn* c, Stream* st) {
     Io* io = c->io;
     Server* s = io->srv;
@@ -867,6 +1000,8 @@ void dispatch(Conn* c, Stream* st) {
     }
     if (p == "/ratelimiter.v1.RateLimiterAdmin/ResetBatch") return dispatch_batch(c, st, msg, K_RESET_BATCH);
     if (p == "/ratelimiter.v1.RateLimiterRefund/RefundBatch") return dispatch_batch(c, st, msg, K_REFUND_BATCH);
+    if (p == "/ratelimiter.v1.RateLimiterMulti/AllowAll") return dispatch_allow_all(c, st, msg, K_ALLOW_ALL);
+    if (p == "/ratelimiter.v1.RateLimiterMulti/AllowAllBatch") return dispatch_allow_all(c, st, msg, K_ALLOW_ALL_BATCH);
     if (p == "/ratelimiter.v1.RateLimiterRefund/Refund") {
         ReqMsg r;
         if (!parse_req(msg, &r)) return respond_err(c, st, GRPC_INTERNAL, "bad RefundRequest");

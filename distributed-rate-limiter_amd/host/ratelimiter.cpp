@@ -409,6 +409,22 @@ public:
         return Error{};
     }
 
+    bool AllowAllMemberOf(const std::string& key, int64_t now_ns, bool intern, AllowAllMember* m) override {
+        m->engine = eng_;
+        m->closed = closed_.load();
+        m->fail_open = cfg_.FailOpen;
+        m->limit = cfg_.Limit;
+        m->alg = host_cfg_.alg;
+        m->cfg_id = cfg_id_;
+        if (!intern) return true;
+        m->ts = now_ns == INT64_MIN ? eng_->clock() : now_ns;
+        m->sms = eng_->server_ms_override != INT64_MIN ? eng_->server_ms_override : rl::floor_div(m->ts, 1000000LL);
+        m->fail_open_reset_at = fail_open_reset_at(m->ts);
+        // a closed limiter does no I/O: AllowN interns before it looks, and so does this
+        m->key_id = eng_->Intern(cfg_.FormatKey(key));
+        return true;
+    }
+
 private:
     int64_t fail_open_reset_at(int64_t t) const {
         if (host_cfg_.alg == rl::ALG_TOKEN_BUCKET) return rl::tb_reset_at((double)t / 1e9, host_cfg_);
@@ -460,6 +476,106 @@ Result NewDeniedResult(int64_t limit, int64_t retry_after, int64_t reset_at) {
 }
 Result NewFailOpenResult() { return Result{true, 0, 0, 0, ZeroTime}; }
 Result NewFailClosedResult() { return Result{false, 0, 0, 0, ZeroTime}; }
+
+Error AllowAll(const Context& ctx, const std::vector<RateLimiter*>& ls, const std::vector<std::string>& keys,
+               const std::vector<int64_t>& n, int64_t now_ns, std::vector<Result>* out, bool* allowed,
+               int32_t* denied_by, bool* bad_arg) {
+    const size_t k = ls.size();
+    if (bad_arg) *bad_arg = true;
+    if (k < 1 || k > RL_ALLOW_ALL_MAX_GROUP || keys.size() != k || n.size() != k || !out) return Error{};
+    std::vector<AllowAllMember> mem(k);
+    for (size_t j = 0; j < k; j++) {
+        if (!ls[j] || !ls[j]->AllowAllMemberOf(keys[j], now_ns, false, &mem[j])) return Error{};
+        if (!mem[j].engine || mem[j].engine != mem[0].engine) return Error{};
+    }
+    if (bad_arg) *bad_arg = false;
+    // AllowN: `if n <= 0 { return nil, ErrInvalidN }` before any I/O
+    for (size_t j = 0; j < k; j++)
+        if (n[j] <= 0) return ErrInvalidN;
+    Engine* eng = mem[0].engine;
+    if (now_ns == INT64_MIN) now_ns = eng->clock();   // one time for the whole group
+    for (size_t j = 0; j < k; j++) ls[j]->AllowAllMemberOf(keys[j], now_ns, true, &mem[j]);
+    out->assign(k, Result{});
+    std::vector<AllowAllEvent> ev(k);
+    for (size_t j = 0; j < k; j++) {
+        ev[j].key = keys[j];
+        ev[j].n = n[j];
+        ev[j].index = (int32_t)j;
+        ev[j].members = k;
+    }
+    auto fail = [&](size_t j, const std::string& why) {
+        Error e = Error::New(Error::Other, "failed to check rate limit: " + why);
+        for (size_t i = 0; i < k; i++) {
+            ev[i].error = e.msg;
+            ev[i].denied_by = (int32_t)j;
+            ls[i]->ObserveAllowAll(ev[i]);
+        }
+        return e;
+    };
+    auto fail_open_result = [&](size_t j) { return Result{true, mem[j].limit, 0, 0, mem[j].fail_open_reset_at}; };
+    // storage errors known before any I/O, per limiter
+    const std::string ctx_cause = ctx.cancelled.load()                                  ? "context canceled"
+                                  : ctx.deadline_ns && eng->clock() >= ctx.deadline_ns ? "context deadline exceeded"
+                                                                                        : "";
+    std::vector<size_t> live;
+    for (size_t j = 0; j < k; j++) {
+        const std::string cause = mem[j].closed ? "engine: client is closed" : ctx_cause;
+        if (cause.empty()) {
+            live.push_back(j);
+            continue;
+        }
+        if (!mem[j].fail_open) return fail(j, cause);   // nothing was sent
+        (*out)[j] = fail_open_result(j);
+    }
+    const size_t m = live.size();
+    std::vector<uint8_t> dec(m, rl::DEC_INVALID), verdict(m, rl::DEC_INVALID), rollback(m, RL_INVALID);
+    if (m) {
+        std::vector<uint64_t> id(m);
+        std::vector<int64_t> ts(m), nn(m), sms(m), rem(m), retry(m), reset(m);
+        std::vector<uint32_t> cfg(m);
+        std::vector<uint8_t> first(m, 0);
+        first[0] = 1;
+        for (size_t i = 0; i < m; i++) {
+            const AllowAllMember& a = mem[live[i]];
+            id[i] = a.key_id; ts[i] = a.ts; nn[i] = n[live[i]]; sms[i] = a.sms; cfg[i] = a.cfg_id;
+        }
+        int rc;
+        std::string cause;
+        {
+            std::lock_guard<std::mutex> g(eng->mu());
+            rc = rl_allow_all_batch(eng->raw(), m, id.data(), ts.data(), nn.data(), cfg.data(), sms.data(), first.data(),
+                                    dec.data(), rem.data(), retry.data(), reset.data(), nullptr, verdict.data(),
+                                    rollback.data());
+            if (rc != RL_OK) cause = engine_error(eng->raw(), rc);
+        }
+        if (rc != RL_OK) {
+            // an engine failure is every live member's storage error
+            for (size_t i = 0; i < m; i++) {
+                if (!mem[live[i]].fail_open) return fail(live[i], cause);
+                (*out)[live[i]] = fail_open_result(live[i]);
+            }
+        } else {
+            for (size_t i = 0; i < m; i++) {
+                const size_t j = live[i];
+                if (dec[i] == rl::DEC_ERROR) return fail(j, "ERR increment or decrement would overflow");
+                if (dec[i] == rl::DEC_INVALID) return fail(j, "engine rejected the request");
+                (*out)[j] = Result{dec[i] == rl::DEC_ALLOWED, mem[j].limit, rem[i], retry[i], reset[i]};
+                if (rollback[i] == RL_REFUND_DONE) ev[j].rolled_back_units = (uint64_t)nn[i];
+            }
+        }
+    }
+    int32_t by = -1;
+    for (size_t j = 0; j < k && by < 0; j++)
+        if (!(*out)[j].Allowed) by = (int32_t)j;
+    if (allowed) *allowed = by < 0;
+    if (denied_by) *denied_by = by;
+    for (size_t j = 0; j < k; j++) {
+        ev[j].allowed = by < 0;
+        ev[j].denied_by = by;
+        ls[j]->ObserveAllowAll(ev[j]);
+    }
+    return Error{};
+}
 
 Error NewTokenBucket(Engine* e, const Config* c, std::unique_ptr<RateLimiter>* out) {
     return construct(e, c, out, rl::ALG_TOKEN_BUCKET);
@@ -803,6 +919,35 @@ extern "C" int rll_refund_n(rll_limiter* l, const char* key, size_t keylen, int6
                             uint8_t* applied, char* err, size_t errlen) {
     if (!l || (!key && keylen)) return RLL_ERR_ARG;
     return rll_refund_many(l, 1, &key, &keylen, &n, &at_ns, now_ns, applied, err, errlen);
+}
+
+extern "C" int rll_allow_all(rll_limiter* const* ls, size_t k, const char* const* keys, const size_t* keylens,
+                             const int64_t* n, int64_t now_ns, int ctx_cancelled, rll_result* out, uint8_t* allowed,
+                             int32_t* denied_by, char* err, size_t errlen) {
+    if (!ls || !keys || !keylens || !n || !out || k < 1 || k > RL_ALLOW_ALL_MAX_GROUP) return RLL_ERR_ARG;
+    std::vector<RateLimiter*> lims(k);
+    std::vector<std::string> ks(k);
+    std::vector<int64_t> nn(n, n + k);
+    for (size_t j = 0; j < k; j++) {
+        if (!ls[j] || (!keys[j] && keylens[j])) return RLL_ERR_ARG;
+        lims[j] = ls[j]->lim.get();
+        ks[j].assign(keys[j] ? keys[j] : "", keylens[j]);
+    }
+    Context ctx;
+    ctx.cancelled.store(ctx_cancelled != 0);
+    std::vector<Result> res;
+    bool ok = false, bad = false;
+    int32_t by = -1;
+    const Error e = AllowAll(ctx, lims, ks, nn, now_ns == RLL_NOW_WALL ? INT64_MIN : now_ns, &res, &ok, &by, &bad);
+    if (bad) return RLL_ERR_ARG;
+    if (e) {
+        put_err(err, errlen, e.msg);
+        return code_of(e);
+    }
+    for (size_t j = 0; j < k; j++) to_c(res[j], &out[j]);
+    if (allowed) *allowed = ok ? 1 : 0;
+    if (denied_by) *denied_by = by;
+    return RLL_OK;
 }
 
 extern "C" int rll_close(rll_limiter* l) {

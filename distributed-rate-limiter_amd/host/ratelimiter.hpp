@@ -146,6 +146,31 @@ struct RefundRequest {
     int64_t at_ns = 0;
 };
 
+class Engine;
+// a limiter's member of an AllowAll group (RateLimiter::AllowAllMemberOf)
+struct AllowAllMember {
+    Engine* engine = nullptr;
+    bool closed = false;          // Close() was called: the storage-error path
+    bool fail_open = false;
+    int64_t limit = 0;
+    int32_t alg = 0;              // RL_ALG_*
+    uint32_t cfg_id = 0;
+    uint64_t key_id = 0;
+    int64_t ts = 0, sms = 0;
+    int64_t fail_open_reset_at = 0;
+};
+// one member's view of a finished AllowAll call (RateLimiter::ObserveAllowAll)
+struct AllowAllEvent {
+    std::string key;
+    int64_t n = 0;
+    int32_t index = 0;            // of this member in its group
+    size_t members = 0;
+    bool allowed = false;         // the group
+    int32_t denied_by = -1;
+    uint64_t rolled_back_units = 0;   // of this member: n when its take was given back
+    std::string error;            // not empty: the call failed with it
+};
+
 class RateLimiter {
 public:
     virtual ~RateLimiter() = default;
@@ -181,11 +206,42 @@ public:
         if (!e && applied) *applied = a[0] != 0;
         return e;
     }
+    // AllowAll (new; ratelimiter::AllowAll below): this limiter's member of a
+    // group check.  With intern == false only the engine, `closed` and the
+    // config fields are filled in; with intern == true also the key id (the
+    // key is interned exactly as AllowN interns it) and the clocks of now_ns
+    // (INT64_MIN: the engine clock).  false: this limiter cannot take part.
+    // A decorator forwards to the limiter it wraps.
+    virtual bool AllowAllMemberOf(const std::string& key, int64_t now_ns, bool intern, AllowAllMember* m) {
+        (void)key, (void)now_ns, (void)intern, (void)m;
+        return false;
+    }
+    // what became of a group this limiter was a member of: a decorator counts
+    // or logs it and forwards it to the limiter it wraps
+    virtual void ObserveAllowAll(const AllowAllEvent& ev) { (void)ev; }
     // request-coalescing path (new): one engine launch for many requests
     virtual void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                             std::vector<BatchOutcome>* out) = 0;
     virtual const Config& config() const = 0;
 };
+
+// AllowAll (new; rl_allow_all_batch): check one request against k limiters of
+// one engine, 1 <= k <= 16, all or nothing: quota stays taken only if every
+// member was allowed; otherwise every member that took something gets it back
+// (a denied window member's INCRBY included), up to Refund's limits.
+// (*out)[j] is limiter j's Result as AllowN would build it; *allowed: every
+// member was allowed; *denied_by: the first member that was not, or -1.  Any
+// n <= 0 is ErrInvalidN before any I/O.  A storage error (closed limiter,
+// cancelled context, engine failure) is handled per limiter: a fail-open
+// limiter contributes its fail-open Result (and is not sent to the engine), a
+// fail-closed one fails the call with "failed to check rate limit: ...".  A
+// member the engine could not execute (RL_ERROR, RL_INVALID) fails the call
+// with that limiter's message, fail-open or not: its group was rolled back, so
+// nothing was admitted.  *bad_arg: k out of range, a null limiter, or
+// limiters of different engines (nothing ran).
+Error AllowAll(const Context& ctx, const std::vector<RateLimiter*>& ls, const std::vector<std::string>& keys,
+               const std::vector<int64_t>& n, int64_t now_ns, std::vector<Result>* out, bool* allowed,
+               int32_t* denied_by, bool* bad_arg);
 
 Error NewTokenBucket(Engine* engine, const Config* config, std::unique_ptr<RateLimiter>* out);
 Error NewSlidingWindow(Engine* engine, const Config* config, std::unique_ptr<RateLimiter>* out);

@@ -168,7 +168,8 @@ class rl_coalescer_stats(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("pad_", C.c_uint32)] + [
         (k, C.c_uint64) for k in ("submitted", "decided", "batches", "max_batch_seen", "pending", "expired",
                                   "cancelled", "gc_runs", "gc_checks", "gc_failures", "peeked", "resets",
-                                  "reset_launches", "refunds", "refund_launches")]
+                                  "reset_launches", "refunds", "refund_launches", "allow_all_groups",
+                                  "allow_all_launches")]
 
 
 vp = C.c_void_p
@@ -177,6 +178,7 @@ BATCH_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp)
 RESET_FN = C.CFUNCTYPE(C.c_int, vp, C.c_uint32, C.c_uint64, C.c_int64)
 RESET_BATCH_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp)
 REFUND_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp)
+ALLOW_ALL_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp)
 INFO_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.POINTER(rl_table_info))
 GC_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(rl_table_info))
 
@@ -184,7 +186,7 @@ GC_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(rl
 class rl_coalescer_backend(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("batch", BATCH_FN), ("reset", RESET_FN), ("table_info", INFO_FN),
                 ("gc", GC_FN), ("user", vp), ("peek", BATCH_FN), ("reset_batch", RESET_BATCH_FN),
-                ("refund", REFUND_FN)]
+                ("refund", REFUND_FN), ("allow_all", ALLOW_ALL_FN)]
 
 _sig = {
     "rl_engine_create": (C.c_int, [C.POINTER(rl_opts), C.POINTER(vp)]),
@@ -205,6 +207,10 @@ _sig = {
     "rl_refund_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]),
     "rl_refund_max": (C.c_uint32, [vp]),
     "rl_refund_grid_cap": (C.c_int, []),
+    "rl_allow_all_batch": (C.c_int, [vp, C.c_size_t] + [vp] * 13),
+    "rl_allow_all_batch_device": (C.c_int, [vp, C.c_size_t] + [vp] * 14),
+    "rl_allow_all_max": (C.c_uint32, [vp]),
+    "rl_allow_all_grid_cap": (C.c_int, []),
     "rl_tally_enable": (C.c_int, [vp, C.POINTER(rl_tally_opts)]),
     "rl_tally_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
     "rl_tally_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
@@ -259,6 +265,7 @@ _sig = {
     "rll_reset_many": (C.c_int, [vp, C.c_size_t, vp, vp, C.c_int64, C.c_char_p, C.c_size_t]),
     "rll_refund_n": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, vp, C.c_char_p,
                                C.c_size_t]),
+    "rll_allow_all": (C.c_int, [vp, C.c_size_t, vp, vp, vp, C.c_int64, C.c_int, vp, vp, vp, C.c_char_p, C.c_size_t]),
     "rll_refund_many": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, C.c_int64, vp, C.c_char_p, C.c_size_t]),
     "rll_close": (C.c_int, [vp]),
     "rll_free": (C.c_int, [vp]),
@@ -278,6 +285,7 @@ _sig = {
     "rl_coalescer_reset": (C.c_int, [vp, C.c_uint64, C.c_int64, C.c_uint32]),
     "rl_coalescer_reset_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
     "rl_coalescer_refund": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
+    "rl_coalescer_allow_all": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]),
     "rl_coalescer_now_ns": (C.c_int64, []),
     "rl_coalescer_submit_deadline": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, C.c_int64, C.POINTER(C.c_uint64)]),
     "rl_coalescer_cancel": (C.c_int, [vp, C.c_uint64]),
@@ -352,6 +360,10 @@ PEEK_GRID_CAP = lib.rl_peek_grid_cap()
 RESET_GRID_CAP = lib.rl_reset_grid_cap()
 # the same of k_refund_add / k_refund_apply
 REFUND_GRID_CAP = lib.rl_refund_grid_cap()
+# the same of k_allow_all_settle
+ALLOW_ALL_GRID_CAP = lib.rl_allow_all_grid_cap()
+# the largest group of an AllowAll call (RL_ALLOW_ALL_MAX_GROUP)
+ALLOW_ALL_MAX_GROUP = 16
 # the same of k_tally
 TALLY_GRID_CAP = lib.rl_tally_grid_cap()
 # the same of k_hot_add / k_hot_pick
@@ -589,6 +601,43 @@ class Engine:
 
     def refund_max(self) -> int:
         return lib.rl_refund_max(self.h)
+
+    def allow_all(self, key, ts, n, cfg, first, server_ms=None, want_tokens=True, want_rollback=True,
+                  check=True) -> Decisions:
+        """rl_allow_all_batch: all-or-nothing checks across several limiters.
+        Member i starts a group when i == 0 or first[i] != 0.  -> the members'
+        Decisions as decide() gives them, plus `.verdict` (the group's verdict
+        on every member) and `.rollback` (REFUND_DONE, REFUND_NOKEY, INVALID:
+        what became of the member's give-back)"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        first = np.ascontiguousarray(first, dtype=np.uint8)
+        sms = None if server_ms is None else np.ascontiguousarray(server_ms, dtype=np.int64)
+        m = key.size
+        assert ts.size == m and n.size == m and cfg.size == m and first.size == m and (sms is None or sms.size == m)
+        out = Decisions(np.empty(m, np.uint8), np.empty(m, np.int64), np.empty(m, np.int64),
+                        np.empty(m, np.int64), np.empty(m, np.float64) if want_tokens else None)
+        out.verdict = np.empty(m, np.uint8)
+        out.rollback = np.empty(m, np.uint8) if want_rollback else None
+        rc = lib.rl_allow_all_batch(self.h, m, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), _ptr(sms), _ptr(first),
+                                    _ptr(out.decision), _ptr(out.remaining), _ptr(out.retry_after_ns),
+                                    _ptr(out.reset_at_ns), _ptr(out.tokens), _ptr(out.verdict), _ptr(out.rollback))
+        if check and rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        out.status = rc
+        return out
+
+    def allow_all_device(self, m, key_p, ts_p, n_p, cfg_p, sms_p, first_p, dec_p, rem_p, retry_p, reset_p, tok_p,
+                         verdict_p, rollback_p=None, stream=None):
+        rc = lib.rl_allow_all_batch_device(self.h, m, key_p, ts_p, n_p, cfg_p, sms_p, first_p, dec_p, rem_p, retry_p,
+                                           reset_p, tok_p, verdict_p, rollback_p, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def allow_all_max(self) -> int:
+        return lib.rl_allow_all_max(self.h)
 
     def tally_enable(self, key_slots=0):
         """rl_tally_enable: allocate the usage tally (key_slots: records of
@@ -1081,6 +1130,28 @@ class RateLimiter:
             return applied.astype(bool), None, rc
         return None, buf.value.decode(), rc
 
+    @staticmethod
+    def allow_all(checks, now_ns=NOW_WALL, cancelled=False):
+        """rll_allow_all: one request against several limiters of one
+        LimiterEngine, all or nothing.  checks: [(limiter, key, n)], 1 to 16.
+        -> (allowed, [Result], denied_by, None, RLL_OK), or (None, None, None,
+        error message, code)"""
+        k = len(checks)
+        hs = (vp * max(k, 1))(*[c[0].h for c in checks])
+        kbs = [c[1].encode() for c in checks]
+        arr = (C.c_char_p * max(k, 1))(*kbs)
+        lens = np.array([len(b) for b in kbs], np.uint64)
+        nn = np.array([c[2] for c in checks], np.int64)
+        res = (rll_result * max(k, 1))()
+        ok, by = C.c_uint8(), C.c_int32(-1)
+        buf = C.create_string_buffer(512)
+        rc = lib.rll_allow_all(C.cast(hs, vp), k, C.cast(arr, vp), _ptr(lens), _ptr(nn), now_ns, 1 if cancelled else 0,
+                               C.cast(res, vp), C.byref(ok), C.byref(by), buf, 512)
+        if rc != RLL_OK:
+            return None, None, None, buf.value.decode(), rc
+        out = [Result(bool(r.allowed), r.limit, r.remaining, r.retry_after_ns, r.reset_at_ns) for r in res[:k]]
+        return bool(ok.value), out, by.value, None, rc
+
     def close(self):
         lib.rll_close(self.h)
 
@@ -1116,7 +1187,7 @@ class Coalescer:
     into engine batches.  `engine` is an Engine (GPU) or, for the CPU tests of
     the batching logic, a Python function with rl_decide_batch's host-array
     signature (the test seam rl_coalescer_create_with_host_backend; `reset`,
-    `table_info`, `gc`, `peek`, `reset_batch`, `refund`: the other backend
+    `table_info`, `gc`, `peek`, `reset_batch`, `refund`, `allow_all`: the other backend
     functions, optional).
 
     gc_interval_ns > 0 turns on the automatic table GC (rl_coalescer_opts);
@@ -1126,7 +1197,7 @@ class Coalescer:
     def __init__(self, engine, max_batch=65536, max_in_flight=3, linger_ns=0, queue_cap=0, reset=None,
                  table_info=None, gc=None, peek=None, gc_interval_ns=0, gc_high_pct=0, gc_margin_ms=0,
                  gc_max_tb_capacity=0, gc_max_win_capacity=0, reset_batch=None, tally_key_slots=0, hot_min=0,
-                 hot_width=0, hot_key_slots=0, hot_weight=HOT_REQUESTS, refund=None):
+                 hot_width=0, hot_key_slots=0, hot_weight=HOT_REQUESTS, refund=None, allow_all=None):
         o = rl_coalescer_opts_hot(hot_min=hot_min, hot_width=hot_width, hot_key_slots=hot_key_slots, hot_weight=hot_weight,
                               max_batch=max_batch, max_in_flight=max_in_flight, gc_high_pct=gc_high_pct,
                               linger_ns=linger_ns, queue_cap=queue_cap, gc_interval_ns=gc_interval_ns,
@@ -1144,7 +1215,8 @@ class Coalescer:
                 gc=GC_FN(gc) if gc else C.cast(None, GC_FN), user=None,
                 peek=BATCH_FN(peek) if peek else C.cast(None, BATCH_FN),
                 reset_batch=RESET_BATCH_FN(reset_batch) if reset_batch else C.cast(None, RESET_BATCH_FN),
-                refund=REFUND_FN(refund) if refund else C.cast(None, REFUND_FN))
+                refund=REFUND_FN(refund) if refund else C.cast(None, REFUND_FN),
+                allow_all=ALLOW_ALL_FN(allow_all) if allow_all else C.cast(None, ALLOW_ALL_FN))
             rc = lib.rl_coalescer_create_with_host_backend(C.byref(self._be), C.byref(o), C.byref(h))
         if rc != RL_OK:
             raise EngineError(rc, "rl_coalescer_create failed")
@@ -1204,6 +1276,24 @@ class Coalescer:
         status = np.empty(key.size, np.uint8)
         rc = lib.rl_coalescer_refund(self.h, key.size, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), _ptr(status))
         return rc, status
+
+    def allow_all(self, key, ts, n, cfg, first, deadline_ns=0):
+        """rl_coalescer_allow_all: one AllowAll call (member i starts a group
+        when i == 0 or first[i] != 0) as one submission in sequence order, one
+        launch, never merged or split; blocks until applied.  -> (rc,
+        (decision, remaining, retry_after_ns, reset_at_ns, verdict))"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        first = np.ascontiguousarray(first, dtype=np.uint8)
+        m = key.size
+        assert ts.size == m and n.size == m and cfg.size == m and first.size == m
+        out = (np.empty(m, np.uint8), np.empty(m, np.int64), np.empty(m, np.int64), np.empty(m, np.int64),
+               np.empty(m, np.uint8))
+        rc = lib.rl_coalescer_allow_all(self.h, m, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), _ptr(first), deadline_ns,
+                                        *[_ptr(x) for x in out])
+        return rc, out
 
     def peek(self, key, ts, n, cfg):
         """rl_coalescer_peek: read-only queries in sequence order; blocks.

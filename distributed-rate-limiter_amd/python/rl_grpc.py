@@ -243,6 +243,27 @@ def refund_batch(stub, items, **kw):
     return [(r.applied, r.error) for r in stub.RefundBatch(req, **kw).results]
 
 
+def multi_stub(channel):
+    """the all-or-nothing service (RateLimiterMulti: AllowAll, AllowAllBatch)"""
+    return Stub(channel, api("ratelimiter.proto"), "RateLimiterMulti")
+
+
+def allow_all(stub, checks, **kw):
+    """RateLimiterMulti.AllowAll of (limiter, key, n) tuples, 1 to 16: quota stays taken only if every check
+    allows -> AllowAllResponse (allowed, results, denied_by, rolled_back)"""
+    a = api("ratelimiter.proto")
+    return stub.AllowAll(a.AllowAllRequest(checks=[a.AllowNRequest(limiter=c[0], key=c[1], n=c[2]) for c in checks]),
+                         **kw)
+
+
+def allow_all_batch(stub, requests, **kw):
+    """RateLimiterMulti.AllowAllBatch of lists of (limiter, key, n) tuples: one launch -> [AllowAllResponse]"""
+    a = api("ratelimiter.proto")
+    req = a.AllowAllBatchRequest(requests=[
+        a.AllowAllRequest(checks=[a.AllowNRequest(limiter=c[0], key=c[1], n=c[2]) for c in r]) for r in requests])
+    return list(stub.AllowAllBatch(req, **kw).responses)
+
+
 def metrics_stub(channel):
     """the observability service (RateLimiterMetrics: Usage)"""
     return Stub(channel, api("ratelimiter.proto"), "RateLimiterMetrics")

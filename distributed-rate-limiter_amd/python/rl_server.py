@@ -383,6 +383,79 @@ class RateLimiterService:
                     out[i] = self.a.RefundResult(applied=int(status[j]) == rl_amd.REFUND_DONE)
         return self.a.RefundBatchResponse(results=out)
 
+    # --- RateLimiterMulti: all-or-nothing checks across limiters ---
+
+    def _group_error(self, checks):
+        """why a group of checks cannot run, or None"""
+        if not 1 <= len(checks) <= 16:
+            return f"checks: need 1 to 16, got {len(checks)}"
+        for r in checks:
+            if r.limiter not in self.by_name:
+                return f"unknown limiter {r.limiter!r}"
+            if r.n <= 0:
+                return ERR_INVALID_N
+        return None
+
+    def _allow_all(self, groups, ctx):
+        """one rl_coalescer_allow_all submission for the groups that can run ->
+        per group (error text | None, gRPC code, AllowAllResponse)"""
+        t = self.clock()
+        out = [None] * len(groups)
+        run, keys, cfg, ns, first, names = [], [], [], [], [], {}
+        for g, checks in enumerate(groups):
+            err = self._group_error(checks)
+            if err:
+                res = [self.a.AllowResponse(error=err) for _ in range(max(1, len(checks)))]
+                out[g] = (err, grpc.StatusCode.INVALID_ARGUMENT,
+                          self.a.AllowAllResponse(allowed=False, results=res, denied_by=-1))
+                continue
+            run.append(g)
+            for j, r in enumerate(checks):
+                names.setdefault(r.limiter, []).append(len(keys))
+                keys.append(r.key.encode())
+                cfg.append(self.by_name[r.limiter].cfg_id)
+                ns.append(r.n)
+                first.append(1 if j == 0 else 0)
+        if run:
+            kid = np.empty(len(keys), np.uint64)
+            for name, pos in names.items():
+                kid[pos] = self._ids(self.by_name[name], [keys[p] for p in pos], len(pos))
+            rc, (dec, rem, retry, reset, verdict) = self.co.allow_all(
+                kid, np.full(len(keys), t, np.int64), np.array(ns, np.int64), np.array(cfg, np.uint32),
+                np.array(first, np.uint8), deadline_ns=self._deadline(ctx))
+            at = 0
+            for g in run:
+                results, rolled, bad = [], [], None
+                for r in groups[g]:
+                    lim = self.by_name[r.limiter]
+                    res, err, code = self._result(lim, t, rc, int(dec[at]), int(rem[at]), int(retry[at]), int(reset[at]))
+                    if res is None:
+                        bad = bad or (err, code)
+                        res = self.a.AllowResponse(error=err)
+                    results.append(res)
+                    took = dec[at] == rl_amd.ALLOWED or (dec[at] == rl_amd.DENIED and lim.alg != rl_amd.TOKEN_BUCKET)
+                    rolled.append(bool(rc == rl_amd.RL_OK and verdict[at] != rl_amd.ALLOWED and took))
+                    at += 1
+                by = next((j for j, x in enumerate(results) if not x.allowed), -1)
+                out[g] = (bad[0] if bad else None, bad[1] if bad else None,
+                          self.a.AllowAllResponse(allowed=by < 0, results=results, denied_by=by, rolled_back=rolled))
+        return out
+
+    def AllowAll(self, req, ctx):
+        """one request against 1 to 16 limiters, all or nothing
+        (rl_coalescer_allow_all): one submission, one group"""
+        err, code, res = self._allow_all([list(req.checks)], ctx)[0]
+        if err:
+            ctx.abort(code, err)
+        return res
+
+    def AllowAllBatch(self, req, ctx):
+        """many such requests: one submission, one launch; a request that
+        cannot run, or that a fail-closed limiter failed, carries the error in
+        its results"""
+        out = self._allow_all([list(r.checks) for r in req.requests], ctx)
+        return self.a.AllowAllBatchResponse(responses=[res for _, _, res in out])
+
     def AllowBatch(self, req, ctx):
         """many AllowN calls: one submission to the coalescer (one GPU batch
         when it fits); per-request errors in AllowResponse.error"""
@@ -432,6 +505,7 @@ def build_server(service: RateLimiterService, address: str, workers: int = 64) -
     for a, sname, impl in ((service.a, "RateLimiter", service), (service.a, "RateLimiterStatus", service),
                            (service.a, "RateLimiterAdmin", service), (service.a, "RateLimiterMetrics", service),
                            (service.a, "RateLimiterTopKeys", service), (service.a, "RateLimiterRefund", service),
+                           (service.a, "RateLimiterMulti", service),
                            (service.h, "Health", service)):
         handlers = {}
         for mname, inp, out in a.services[sname]:

@@ -124,6 +124,9 @@ typedef struct rl_coalescer_stats {
     uint64_t refunds;        /* refund requests that contributed (RL_REFUND_DONE; rl_coalescer_refund); not in
                                 submitted / decided */
     uint64_t refund_launches; /* refund submissions launched: one launch each, never merged */
+    uint64_t allow_all_groups;   /* groups of the AllowAll submissions launched (rl_coalescer_allow_all); their
+                                    members count in submitted / decided */
+    uint64_t allow_all_launches; /* AllowAll submissions launched: one launch each, never merged; not in batches */
 } rl_coalescer_stats;
 
 /* Signature of rl_decide_batch (host arrays, synchronous).  A backend of this
@@ -141,6 +144,11 @@ typedef int (*rl_reset_batch_fn)(void* user, size_t m, const uint64_t* key_id, c
  * status (RL_REFUND_DONE / RL_REFUND_NOKEY / RL_INVALID; never null here) */
 typedef int (*rl_refund_fn)(void* user, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
                             const uint32_t* cfg_id, uint8_t* status);
+/* rl_allow_all_batch's signature without the store clock, the tokens and the rollback: one AllowAll call
+ * (decide, settle, refund) */
+typedef int (*rl_allow_all_fn)(void* user, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                               const uint32_t* cfg_id, const uint8_t* first, uint8_t* decision, int64_t* remaining,
+                               int64_t* retry_after_ns, int64_t* reset_at_ns, uint8_t* verdict);
 /* table counts / GC for the host backend (rl_table_info_get / rl_table_gc) */
 typedef int (*rl_info_fn)(void* user, int64_t now_ms, rl_table_info* out);
 typedef int (*rl_gc_fn)(void* user, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
@@ -161,6 +169,8 @@ typedef struct rl_coalescer_backend {
                                       `reset`, one call per key; its RL_EINVAL is that request's RL_INVALID */
     rl_refund_fn refund;     /* nullable (and absent from a shorter struct): rl_coalescer_refund is then
                                 RL_EINVAL */
+    rl_allow_all_fn allow_all; /* nullable (and absent from a shorter struct): rl_coalescer_allow_all is then
+                                  RL_EINVAL */
 } rl_coalescer_backend;
 
 /* Coalescer over a GPU engine, on the device current on the calling thread
@@ -243,6 +253,28 @@ int rl_coalescer_reset_batch(rl_coalescer* c, size_t m, const uint64_t* key_id, 
  * RL_EINVAL over a host backend without `refund`. */
 int rl_coalescer_refund(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
                         const uint32_t* cfg_id, uint8_t* status);
+/* One AllowAll call (rl_allow_all_batch_device, include/rl_engine.h; the store
+ * clock of a member is floor(ts_ns / 1e6)): m members in groups -- member i
+ * starts a group when i == 0 or first[i] != 0 --, all or nothing per group, as
+ * one submission in sequence order.  Blocks until applied.  Every member gets
+ * its own decision, remaining, retry_after_ns and reset_at_ns (the decide's,
+ * before any give-back) and `verdict`, its group's verdict.  A submission is
+ * one launch and one engine call: never split (above max_batch, or above the
+ * engine's rl_allow_all_max: RL_EINVAL) and never merged with another -- merging
+ * would make the denials on a rolled-back group's transient take, and the
+ * refund sums of a bucket, depend on the timing of the queue.  A full queue
+ * refuses it (RL_EAGAIN).  Its members insert keys: they count in the automatic
+ * GC's insert budgets and in stats.submitted / .decided; its groups and launch
+ * count in stats.allow_all_groups / .allow_all_launches.  deadline_ns (0 =
+ * none) and cancellation behave as for a decide submission: one whose deadline
+ * passed before its launch is dropped unapplied (RL_EDEADLINE).  With the
+ * usage tally or the top keys on, the members are counted with their own
+ * decisions -- what each limiter's script did --, as a decide batch is; the
+ * give-backs are not in the tally, as a refund's are not.  RL_EINVAL over a
+ * host backend without `allow_all`. */
+int rl_coalescer_allow_all(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                           const uint32_t* cfg_id, const uint8_t* first, int64_t deadline_ns, uint8_t* decision,
+                           int64_t* remaining, int64_t* retry_after_ns, int64_t* reset_at_ns, uint8_t* verdict);
 /* Read-only queries (rl_peek_batch_device, include/rl_engine.h): for each
  * request the Result AllowN would return, against the state left by every
  * request submitted before the call and none submitted after it; nothing is

@@ -231,6 +231,78 @@ uint32_t rl_refund_max(rl_engine* e);
  * size); a larger call strides */
 int rl_refund_grid_cap(void);
 
+/* AllowAll: check one request against several limiters, all or nothing.  A
+ * call carries m member requests (key_id, ts_ns, n, cfg_id, server_ms) as a
+ * decide batch does, and a byte array first[m]: member i starts a new group
+ * when i == 0 or first[i] != 0, and a group is a maximal run of members (every
+ * byte array is a grouping).  A group has at most RL_ALLOW_ALL_MAX_GROUP
+ * members; a longer run is one group whose verdict is RL_INVALID.  The call has
+ * exactly the effect of three steps, placed between the batches enqueued before
+ * and after it:
+ *   1. decide   rl_decide_batch_device on the m members as one batch in array
+ *               order: decision, remaining, retry_after_ns, reset_at_ns and
+ *               tokens of every member exactly as that call gives them
+ *   2. settle   verdict[i], the same for every member of a group: the most
+ *               severe decision of the group, RL_INVALID > RL_ERROR > RL_DENIED
+ *               > RL_ALLOWED.  The give-back g[i] is n[i] when the verdict is
+ *               not RL_ALLOWED and the member took something -- a token bucket
+ *               that allowed; a window limiter that allowed or denied (a denied
+ *               window request still ran INCRBY, fixedwindow.go:22,
+ *               slidingwindow.go:24) -- and 0 otherwise (an RL_ERROR or
+ *               RL_INVALID member stored nothing)
+ *   3. refund   one rl_refund_batch_device call over the same (key_id, ts_ns,
+ *               cfg_id, server_ms) with n = g, with exactly that call's
+ *               semantics: per-target sums, the %.14g store, DEL at zero,
+ *               nothing stored for RL_REFUND_NOKEY.  Its status comes back as
+ *               rollback[i] (nullable): RL_REFUND_DONE the amount was given
+ *               back, RL_REFUND_NOKEY there was no live target (a window under
+ *               one second, whose TTL is 0), RL_INVALID nothing was asked back
+ * A failed check therefore takes nothing from any limiter, up to Refund's
+ * limits: a bucket's last_refill and the TTLs are not rolled back, and %.14g
+ * requantises the stored tokens.  The verb is conservative: within one call a
+ * later group sees the quota an earlier group took before that group is rolled
+ * back, so it may be denied where a strictly sequential all-or-nothing would
+ * admit it; it is never admitted on quota a sequential run would not have.  A
+ * member's `remaining` is the decide's value, taken before any give-back.  A
+ * one-member group is AllowN, plus the give-back of a denied window member's
+ * INCRBY.
+ * m <= rl_allow_all_max(e) = rl_refund_max(e), else RL_EINVAL: a call is never
+ * split (the refund's sum rule).  m == 0 is RL_OK without a launch; null input
+ * arrays (or a null verdict) with m > 0 are RL_EINVAL.  rl_stats moves as for
+ * the decide; the tally and the top keys are not touched.  The first call
+ * allocates the engine's scratch for g.  Host arrays; synchronous; returns the
+ * sticky device status as rl_decide_batch does (RL_ENOMEM: the table filled and
+ * some members were rejected).  "A failed check takes nothing" is a statement
+ * about verdicts, not about return codes: a non-RL_OK return after the decide
+ * was enqueued (a HIP runtime error in the event wait, the settle launch or the
+ * refund: RL_EDEVICE) leaves the members' takes in place and gives nothing
+ * back.  That is a device-error path only; argument errors and failed
+ * allocations return before anything is taken. */
+#define RL_ALLOW_ALL_MAX_GROUP 16
+int rl_allow_all_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                       const uint32_t* cfg_id, const int64_t* server_ms, const uint8_t* first,
+                       uint8_t* decision, int64_t* remaining, int64_t* retry_after_ns, int64_t* reset_at_ns,
+                       double* tokens, uint8_t* verdict, uint8_t* rollback);
+/* Same, with device pointers: the decide enqueued on `stream` as
+ * rl_decide_batch_device does, the settle kernel on `stream` behind it, then
+ * the refund on the engine's replay stream, ordered as rl_refund_batch_device;
+ * `stream` waits for it.  The give-backs are made on the device, so the refund
+ * always waits for `stream`, whatever RL_OPT_PIPELINE says: under that flag
+ * this call holds the next batch's replay until this batch's finish has run.
+ * That is the price of the verb; plain batches pay nothing for it.  Calls may
+ * come from different streams: each call's settle kernel waits for the previous
+ * call's refund before it writes the scratch again. */
+int rl_allow_all_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                              const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                              const uint8_t* first, uint8_t* decision, int64_t* remaining,
+                              int64_t* retry_after_ns, int64_t* reset_at_ns, double* tokens, uint8_t* verdict,
+                              uint8_t* rollback, void* stream);
+/* the largest AllowAll call: rl_refund_max(e) */
+uint32_t rl_allow_all_max(rl_engine* e);
+/* members one settle launch covers with one member per thread (grid cap x
+ * block size); a larger call strides */
+int rl_allow_all_grid_cap(void);
+
 /* Peek: read-only quota queries.  For each request, the outputs
  * rl_decide_batch would give for it at (ts_ns, server_ms) against the state
  * left by every batch enqueued before the call -- and nothing changes: no key

@@ -146,6 +146,30 @@ int rll_refund_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int6
  * Any n <= 0 fails the whole call with RLL_ERR_INVALID_N, nothing applied. */
 int rll_refund_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens, const int64_t* n,
                     const int64_t* at_ns, int64_t now_ns, uint8_t* applied, char* err, size_t errlen);
+/* AllowAll: check one request against k limiters, 1 <= k <= 16, all on one
+ * rll_engine (else RLL_ERR_ARG), all or nothing (rl_allow_all_batch,
+ * include/rl_engine.h): one group of one engine call.  Quota stays taken only
+ * if every member was allowed; otherwise every member that took something gets
+ * it back, a denied window member's count included, up to Refund's limits.
+ * out[j] is limiter j's Result as rll_allow_n would build it (its remaining is
+ * the value before any give-back); *allowed (nullable) is 1 iff every member
+ * was allowed; *denied_by (nullable) the index of the first member that was
+ * not, or -1.  Any n <= 0 is RLL_ERR_INVALID_N before any I/O.  A key never
+ * seen is interned exactly as rll_allow_n interns it.  A storage error (a
+ * closed limiter, a cancelled context, an engine failure) is handled per
+ * limiter: a fail-open limiter contributes its fail-open Result and is not
+ * sent to the engine, a fail-closed one fails the call with RLL_ERR_FAILED as
+ * rll_allow_n does -- before anything is sent when the error is known then.
+ * A member the engine could not execute (RL_ERROR: INCRBY overflow) is
+ * RLL_ERR_FAILED with that limiter's message; its group was rolled back.  The
+ * metrics decorator of each member counts the group
+ * (rate_limiter_allow_all_total{allowed}) and the units of its own take that
+ * were given back (rate_limiter_allow_all_rolled_back_units_total{algorithm}),
+ * exposed once the verb was used; the logging decorator logs a denied group at
+ * debug and a failed call at error level. */
+int rll_allow_all(rll_limiter* const* ls, size_t k, const char* const* keys, const size_t* keylens,
+                  const int64_t* n, int64_t now_ns, int ctx_cancelled, rll_result* out /* k */, uint8_t* allowed,
+                  int32_t* denied_by, char* err, size_t errlen);
 int rll_close(rll_limiter* l);   /* Close(): later calls take the storage-error path */
 int rll_free(rll_limiter* l);
 
