@@ -3,7 +3,8 @@
 // Each is one chain op -- one kernel, Refund's two -- on the engine's `chain`
 // stream between two replays (chain_op, rl_engine_impl.h).  AllowAll
 // (rl_allow_all.h) composes a decide, its settle kernel on the caller's stream
-// and a refund.
+// and a refund; the routed AllowAll's settle (rl_allow_all_settle_device) is
+// the second instantiation of that kernel's text.
 // A code object of its own: that of the decision kernels (rl_engine.hip) does
 // not change with it.
 #include <hip/hip_runtime.h>
@@ -412,6 +413,23 @@ static int allow_all_warm_up(rl_engine* e) {
 extern "C" uint32_t rl_allow_all_max(rl_engine* e) { return e ? refund_max(e) : 0; }
 
 extern "C" int rl_allow_all_grid_cap(void) { return ALLOW_ALL_GRID * ALLOW_ALL_BLOCK; }
+
+// The sender's settle of a routed AllowAll (include/rl_route.h): one kernel on
+// the caller's stream.  It takes no engine stream, scratch or table, only the
+// device config table for `alg`.
+extern "C" int rl_allow_all_settle_device(rl_engine* e, size_t m, const uint8_t* first, const uint32_t* cfg_id,
+                                          const int64_t* n, const uint8_t* decision, uint8_t* verdict, int64_t* g,
+                                          uint8_t* sel, void* stream) {
+    if (!e || (m && (!first || !cfg_id || !n || !decision || !verdict || !g || !sel))) return RL_EINVAL;
+    if (m > e->max_batch) return fail(e, RL_EINVAL, "routed settle above the engine's max_batch");
+    if (m == 0) return RL_OK;
+    (void)hipSetDevice(e->device);
+    k_allow_all_settle_routed<<<grid_for(m, ALLOW_ALL_BLOCK, ALLOW_ALL_GRID), ALLOW_ALL_BLOCK, 0,
+                                (hipStream_t)stream>>>((uint64_t)m, first, cfg_id, n, decision, e->d_cfg,
+                                                       (uint32_t)e->h_cfg.size(), verdict, g, sel);
+    HIPCHK(e, hipGetLastError());
+    return RL_OK;
+}
 
 extern "C" int rl_allow_all_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
                                          const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,

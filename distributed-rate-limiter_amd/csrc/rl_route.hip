@@ -75,9 +75,13 @@ struct PackSum {
 
 
 // per-tile owner counts: tile_cnt[tile * world + o]; the tile's summary in
-// tile_sum[tile] (no global atomics: k_route_scan reduces the tiles)
+// tile_sum[tile] (no global atomics: k_route_scan reduces the tiles).
+// SEL (rl_route_pack_sel): only requests with sel[i] != 0 are counted; the
+// summary still covers every request of the batch (the store clock).
+template <bool SEL>
 __global__ __launch_bounds__(RT_BLOCK) void k_route_hist(uint32_t m, const uint64_t* __restrict__ key,
-                                                         const int64_t* __restrict__ ts, uint32_t world,
+                                                         const int64_t* __restrict__ ts,
+                                                         const uint8_t* __restrict__ sel, uint32_t world,
                                                          uint32_t* __restrict__ tile_cnt, PackSum* tile_sum) {
     __shared__ uint32_t s_cnt[MAX_WORLD];
     __shared__ unsigned long long s_lo[RT_BLOCK / 64], s_hi[RT_BLOCK / 64];
@@ -94,7 +98,8 @@ __global__ __launch_bounds__(RT_BLOCK) void k_route_hist(uint32_t m, const uint6
     for (int j = 0; j < RT_ITEMS; j++) {
         const uint32_t i = base + j * RT_BLOCK + threadIdx.x;
         const bool ok = i < m;
-        const uint32_t own = ok ? owner_of(key[i], world) : 0u;
+        const bool in = SEL ? (ok && sel[i] != 0) : ok;   // counted for its owner
+        const uint32_t own = in ? owner_of(key[i], world) : 0u;
         const int64_t t = ok ? ts[i] : 0;
         // a wave's 64 requests are consecutive: the predecessor's ts is the
         // lane below (lane 0 loads it)
@@ -103,8 +108,8 @@ __global__ __launch_bounds__(RT_BLOCK) void k_route_hist(uint32_t m, const uint6
         if (ok && i > 0 && tp > t) uns = 1;
         // one LDS add per owner per wave (not per request: at small world
         // every request of a tile would hit one counter)
-        const uint64_t peers = owner_peers(own, world, ok);
-        if (ok && (peers & lt) == 0) atomicAdd(&s_cnt[own], (uint32_t)__popcll(peers));
+        const uint64_t peers = owner_peers(own, world, in);
+        if (in && (peers & lt) == 0) atomicAdd(&s_cnt[own], (uint32_t)__popcll(peers));
         if (ok) {
             const unsigned long long b = bias(t);
             lo = b < lo ? b : lo;
@@ -198,11 +203,15 @@ __global__ __launch_bounds__(RT_BLOCK) void k_route_scan(uint32_t tiles, uint32_
 }
 
 // stable scatter of the requests into their owners' buckets; past a bucket's
-// capacity a request is dropped (slot UINT32_MAX, sticky RS_OVERFLOW)
+// capacity a request is dropped (slot RL_SLOT_DROPPED, sticky RS_OVERFLOW).
+// SEL (rl_route_pack_sel): a request with sel[i] == 0 takes no position and
+// gets slot RL_SLOT_SKIPPED.
+template <bool SEL>
 __global__ __launch_bounds__(RT_BLOCK) void k_route_scatter(uint32_t m, const uint64_t* __restrict__ key,
                                                             const int64_t* __restrict__ ts,
                                                             const int64_t* __restrict__ n,
-                                                            const uint32_t* __restrict__ cfg, uint32_t world,
+                                                            const uint32_t* __restrict__ cfg,
+                                                            const uint8_t* __restrict__ sel, uint32_t world,
                                                             uint32_t cap, const uint32_t* __restrict__ tile_off,
                                                             rl_route_rec* __restrict__ send,
                                                             uint32_t* __restrict__ slot, uint32_t* status) {
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(RT_BLOCK) void k_route_scatter(uint32_t m, const ui
 #pragma unroll
     for (int j = 0; j < RT_ITEMS; j++) {
         const uint32_t i = base + j * 64 + lane;
-        const bool ok = i < m;
+        const bool ok = SEL ? (i < m && sel[i] != 0) : i < m;
         own[j] = ok ? owner_of(key[i], world) : 0u;
         const uint64_t peers = owner_peers(own[j], world, ok);
         if (ok) {
@@ -244,9 +253,13 @@ __global__ __launch_bounds__(RT_BLOCK) void k_route_scatter(uint32_t m, const ui
     for (int j = 0; j < RT_ITEMS; j++) {
         const uint32_t i = base + j * 64 + lane;
         if (i >= m) continue;
+        if (SEL && sel[i] == 0) {
+            slot[i] = RL_SLOT_SKIPPED;
+            continue;
+        }
         const uint32_t p = s_wcnt[wave][own[j]] + rank[j];
         if (p >= cap) {
-            slot[i] = 0xffffffffu;
+            slot[i] = RL_SLOT_DROPPED;
             over = true;
             continue;
         }
@@ -546,8 +559,10 @@ __global__ __launch_bounds__(RT_BLOCK) void k_bm_merge(uint32_t level, uint32_t 
 // 10 us (5.9 TB/s of its 61 bytes per request; profiles/r5m_route_unpack.txt).
 __device__ inline void unpack_one(uint32_t s, const rl_route_res* __restrict__ back, uint32_t& d, int64_t& rm,
                                   int64_t& rt, int64_t& rs) {
-    if (s == 0xffffffffu) {   // dropped at the sender: never executed
-        d = RL_DROPPED;
+    if (s >= RL_SLOT_SKIPPED) {   // not sent (real slots stay below 2^30)
+        // dropped at the sender: never executed; skipped by rl_route_pack_sel:
+        // nothing was asked
+        d = s == RL_SLOT_DROPPED ? RL_DROPPED : RL_INVALID;
         rm = rt = rs = 0;
         return;
     }
@@ -676,20 +691,35 @@ extern "C" int rl_route_owner(rl_router* r, size_t m, const uint64_t* key, uint3
     return hipGetLastError() == hipSuccess ? RL_OK : RL_EDEVICE;
 }
 
-extern "C" int rl_route_pack(rl_router* r, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
-                             const uint32_t* cfg, rl_route_rec* send, int64_t* send_info, uint32_t* slot,
-                             void* stream) {
-    if (!r || !send_info || m > r->max_batch || (m && (!key || !ts || !n || !cfg || !send || !slot)))
+// the pack of a whole batch (SEL = false, sel unused) or of a selection of it
+template <bool SEL>
+static int route_pack(rl_router* r, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                      const uint32_t* cfg, const uint8_t* sel, rl_route_rec* send, int64_t* send_info, uint32_t* slot,
+                      void* stream) {
+    if (!r || !send_info || m > r->max_batch || (m && (!key || !ts || !n || !cfg || !send || !slot)) ||
+        (SEL && m && !sel))
         return RL_EINVAL;
     (void)hipSetDevice(r->device);
     hipStream_t s = (hipStream_t)stream;
     const uint32_t tiles = (uint32_t)((m + RT_TILE - 1) / RT_TILE);
-    if (m) k_route_hist<<<tiles, RT_BLOCK, 0, s>>>((uint32_t)m, key, ts, r->world, r->tile_cnt, r->psum);
+    if (m) k_route_hist<SEL><<<tiles, RT_BLOCK, 0, s>>>((uint32_t)m, key, ts, sel, r->world, r->tile_cnt, r->psum);
     k_route_scan<<<r->world, RT_BLOCK, 0, s>>>(tiles, r->world, r->cap, r->tile_cnt, r->tile_off, r->psum, send_info);
     if (m)
-        k_route_scatter<<<tiles, RT_BLOCK, 0, s>>>((uint32_t)m, key, ts, n, cfg, r->world, r->cap, r->tile_off, send,
-                                                   slot, r->d_status);
+        k_route_scatter<SEL><<<tiles, RT_BLOCK, 0, s>>>((uint32_t)m, key, ts, n, cfg, sel, r->world, r->cap,
+                                                        r->tile_off, send, slot, r->d_status);
     return hipGetLastError() == hipSuccess ? RL_OK : RL_EDEVICE;
+}
+
+extern "C" int rl_route_pack(rl_router* r, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                             const uint32_t* cfg, rl_route_rec* send, int64_t* send_info, uint32_t* slot,
+                             void* stream) {
+    return route_pack<false>(r, m, key, ts, n, cfg, nullptr, send, send_info, slot, stream);
+}
+
+extern "C" int rl_route_pack_sel(rl_router* r, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                                 const uint32_t* cfg, const uint8_t* sel, rl_route_rec* send, int64_t* send_info,
+                                 uint32_t* slot, void* stream) {
+    return route_pack<true>(r, m, key, ts, n, cfg, sel, send, send_info, slot, stream);
 }
 
 extern "C" int rl_route_merge(rl_router* r, const rl_route_rec* recv, const int64_t* recv_info, uint32_t* order,

@@ -311,6 +311,8 @@ _sig = {
     "rl_stream_destroy": (C.c_int, [vp]),
     "rl_router_capacity": (C.c_uint32, [vp]),
     "rl_route_pack": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
+    "rl_route_pack_sel": (C.c_int, [vp, C.c_size_t] + [vp] * 9),
+    "rl_allow_all_settle_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
     "rl_route_merge": (C.c_int, [vp] + [vp] * 6),
     "rl_route_unpack": (C.c_int, [vp, C.c_size_t] + [vp] * 7),
     "rl_decide_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 6),
@@ -639,6 +641,15 @@ class Engine:
     def allow_all_max(self) -> int:
         return lib.rl_allow_all_max(self.h)
 
+    def allow_all_settle(self, m, first_p, cfg_p, n_p, dec_p, verdict_p, g_p, sel_p, stream=None):
+        """rl_allow_all_settle_device (include/rl_route.h): the sender's settle
+        of a routed AllowAll on the unpacked decisions (RL_DROPPED included) ->
+        verdict, give-back g and selection sel; device pointers, one kernel on
+        `stream`"""
+        rc = lib.rl_allow_all_settle_device(self.h, m, first_p, cfg_p, n_p, dec_p, verdict_p, g_p, sel_p, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
     def tally_enable(self, key_slots=0):
         """rl_tally_enable: allocate the usage tally (key_slots: records of
         the throttled-key table, 0 = 65536)"""
@@ -831,6 +842,8 @@ def release_dedicated_streams():
 # rl_route.h
 RL_EOVERFLOW = -75
 DROPPED = 4
+SLOT_DROPPED = 0xffffffff
+SLOT_SKIPPED = 0xfffffffe
 
 
 class Router:
@@ -868,6 +881,12 @@ class Router:
 
     def pack(self, m, key, ts, n, cfg, send, send_info, slot, stream):
         self._chk(lib.rl_route_pack(self.h, m, key, ts, n, cfg, send, send_info, slot, stream), "rl_route_pack")
+
+    def pack_sel(self, m, key, ts, n, cfg, sel, send, send_info, slot, stream):
+        """rl_route_pack_sel: pack() of the requests with sel[i] != 0; the
+        others get slot RL_SLOT_SKIPPED"""
+        self._chk(lib.rl_route_pack_sel(self.h, m, key, ts, n, cfg, sel, send, send_info, slot, stream),
+                  "rl_route_pack_sel")
 
     def merge(self, recv, recv_info, order, sms, count, stream):
         self._chk(lib.rl_route_merge(self.h, recv, recv_info, order, sms, count, stream), "rl_route_merge")

@@ -106,6 +106,13 @@ class RoutedPipeline:
     exchange never waits for the engine of the step before it, and its merge
     and grouping wait only for the engine of step b - L - 1, which the
     engine's three buffer sets make it wait for anyway at L = 1.
+    allow_all(b, ...) is two steps whose second is packed from the first's
+    results, so step b's result side cannot wait: the call first issues every
+    pending result side, then Req(b), Res(b) at once, Req(b + 1), and defers
+    Res(b + 1) by the usual rule -- ... Res(pending), Req(b), Res(b),
+    Req(b + 1), then as above.  Every rank calls allow_all at the same step
+    number, so this too is one order on every rank, and each collective still
+    waits for the last one issued on the other group.
 
     decide(m_max, count, recv, order, sms, res, in_stream, out_stream) runs
     the owner's engine on the merged batch (rl_decide_routed_device_io;
@@ -127,12 +134,21 @@ class RoutedPipeline:
     rl_reset_routed_device / rl_refund_routed_device with out_stream) or
     peek_ev / reset_ev / refund_ev (that of decide_ev).  Every rank must give a
     step the same kind.  The engine orders
-    the step after every step issued before it and before every later one."""
+    the step after every step issued before it and before every later one.
+
+    allow_all(b, ...) (settle=: Engine.allow_all_settle) checks each request
+    against several limiters, all or nothing, wherever their keys live: decide
+    step b, the settle on U, and refund step b + 1 packed with ops.pack_sel from
+    the settle's give-backs (include/rl_route.h)."""
 
     def __init__(self, ops, decide, world, max_batch, device, pg_req=None, pg_res=None, depth=4, exchange=None,
                  staged=False, lookahead=None, ordered=True, decide_ev=None, *, peek=None, peek_ev=None, reset=None,
-                 reset_ev=None, refund=None, refund_ev=None):
+                 reset_ev=None, refund=None, refund_ev=None, settle=None):
         self.ops, self.decide, self.world = ops, decide, world
+        # settle(m, first, cfg, n, dec, verdict, g, sel, stream): the sender's
+        # settle of allow_all (rl_allow_all_settle_device; device pointers)
+        self.settle = settle
+        self._aa = None               # allow_all's scratch (g, sel, the refund step's unused outputs)
         self.dev = torch.device(device)
         self.cuda = self.dev.type == "cuda"
         self.pg_req, self.pg_res = pg_req, pg_res
@@ -259,7 +275,6 @@ class RoutedPipeline:
         if call is None and call_ev is None:
             raise ValueError(f"RoutedPipeline: a {_OP_NAMES[op]} step needs the pipeline built with "
                              f"{_OP_NAMES[op]}= or {_OP_NAMES[op]}_ev=")
-        s = self.slots[b % self.depth]
         m = key.numel()
         assert m <= self.max_batch
         if n is None:
@@ -268,6 +283,19 @@ class RoutedPipeline:
             if self._zero_n is None:
                 self._zero_n = torch.zeros(self.max_batch, dtype=torch.int64, device=self.dev)
             n = self._zero_n[:m]
+        self._request_side(b, key, ts, n, cfg, call, call_ev)
+        self._pend.append((b, self.slots[b % self.depth], m, dec, rem, retry, reset, call_ev is not None))
+        done = []
+        while len(self._pend) > self.lookahead:
+            done.append(self._result_side(*self._pend.pop(0)))
+        return done
+
+    def _request_side(self, b, key, ts, n, cfg, call, call_ev, sel=None, after=None):
+        """pack (of the requests with sel != 0, when given), request exchange,
+        merge and the owner's engine call of step b, on R (after the event
+        `after`, when given)"""
+        s = self.slots[b % self.depth]
+        m = key.numel()
         p, sp = self._p, self._sp
         R = self.R
         recv = s["recv"] if self.exchange else s["send"]
@@ -275,7 +303,13 @@ class RoutedPipeline:
         with _ctx(R):
             if s["ev_done"] is not None:
                 R.wait_event(s["ev_done"])   # the set's previous step has unpacked
-            self.ops.pack(m, p(key), p(ts), p(n), p(cfg), p(s["send"]), p(s["scnt"]), p(s["slot"]), sp(R))
+            if after is not None:
+                R.wait_event(after)
+            if sel is None:
+                self.ops.pack(m, p(key), p(ts), p(n), p(cfg), p(s["send"]), p(s["scnt"]), p(s["slot"]), sp(R))
+            else:
+                self.ops.pack_sel(m, p(key), p(ts), p(n), p(cfg), p(sel), p(s["send"]), p(s["scnt"]), p(s["slot"]),
+                                  sp(R))
             if self.exchange:
                 if self._ev_res is not None and self.ordered and self.pg_res is not self.pg_req:
                     R.wait_event(self._ev_res)   # after the last result collective issued
@@ -291,8 +325,48 @@ class RoutedPipeline:
             else:
                 call(self.m_max, p(s["count"]), p(recv), p(s["order"]), p(s["sms"]), p(s["res"]), sp(R),
                      sp(self.U))
-        self._pend.append((b, s, m, dec, rem, retry, reset, call_ev is not None))
-        done = []
+
+    def allow_all(self, b, key, ts, n, cfg, first, dec, rem, retry, reset, verdict, rollback):
+        """a routed AllowAll (include/rl_route.h) of the M members (key, ts, n,
+        cfg; `first` uint8: member i starts a group when i == 0 or first[i] !=
+        0) as the steps b and b + 1: a decide step, whose results reach
+        dec/rem/retry/reset at once, the settle into `verdict` (uint8), and a
+        refund step of the give-backs, whose statuses reach `rollback` (uint8)
+        once step b + 1's result side is issued, as any step's.  Every rank
+        calls it at the same step number.  Nothing is read by the host.
+        Returns the [(b', stream)] whose result sides this call issued."""
+        call, call_ev = self._calls[OP_DECIDE]
+        rcall, rcall_ev = self._calls[OP_REFUND]
+        if self.settle is None:
+            raise ValueError("RoutedPipeline: allow_all needs the pipeline built with settle=")
+        if call is None and call_ev is None:
+            raise ValueError("RoutedPipeline: allow_all needs a decide call")
+        if rcall is None and rcall_ev is None:
+            raise ValueError("RoutedPipeline: allow_all needs the pipeline built with refund= or refund_ev=")
+        if self.depth < 2:
+            raise ValueError("RoutedPipeline: allow_all needs depth >= 2 (its two steps hold a buffer set each)")
+        m = key.numel()
+        assert m <= self.max_batch
+        if self._aa is None:
+            d, M = self.dev, self.max_batch
+            self._aa = dict(g=torch.zeros(M, dtype=torch.int64, device=d),
+                            sel=torch.zeros(M, dtype=torch.uint8, device=d),
+                            out=[torch.empty(M, dtype=torch.int64, device=d) for _ in range(3)],
+                            ev_packed=None)
+        A = self._aa
+        p, sp, U = self._p, self._sp, self.U
+        done = self.flush()                       # Res(pending): the same order on every rank
+        self._request_side(b, key, ts, n, cfg, call, call_ev)
+        done.append(self._result_side(b, self.slots[b % self.depth], m, dec, rem, retry, reset, call_ev is not None))
+        with _ctx(U):
+            if A["ev_packed"] is not None:
+                U.wait_event(A["ev_packed"])      # the previous call's pack has read g and sel
+            self.settle(m, p(first), p(cfg), p(n), p(dec), p(verdict), p(A["g"]), p(A["sel"]), sp(U))
+            settled = self._record(U)
+        self._request_side(b + 1, key, ts, A["g"][:m], cfg, rcall, rcall_ev, sel=A["sel"], after=settled)
+        A["ev_packed"] = self._record(self.R)
+        self._pend.append((b + 1, self.slots[(b + 1) % self.depth], m, rollback, *(o[:m] for o in A["out"]),
+                           rcall_ev is not None))
         while len(self._pend) > self.lookahead:
             done.append(self._result_side(*self._pend.pop(0)))
         return done

@@ -44,6 +44,8 @@
  *                               here instead; see there)
  *            equal-split all-to-all of the result buckets back
  *   sender   rl_route_unpack    results to the caller's order
+ * (a routed AllowAll is two such steps with a settle on the sender between
+ * them and rl_route_pack_sel packing the second; see rl_allow_all_settle_device)
  *
  * The store's clock (Redis TTLs) is one clock that never goes back: request
  * p of step b expires keys at server_ms = max(floor(arrival_p / 1e6), the
@@ -131,6 +133,25 @@ int rl_route_owner(rl_router* r, size_t m, const uint64_t* key, uint32_t* owner,
  * (tests/test_route_gpu.py::test_route_dropped_request_advances_store_clock). */
 int rl_route_pack(rl_router* r, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
                   const uint32_t* cfg, rl_route_rec* send, int64_t* send_info, uint32_t* slot, void* stream);
+
+#define RL_SLOT_DROPPED 0xffffffffu   /* slot[i]: dropped, its owner's bucket was full */
+#define RL_SLOT_SKIPPED 0xfffffffeu   /* slot[i]: not selected (rl_route_pack_sel) */
+
+/* sender: rl_route_pack of the requests with sel[i] != 0 (a byte per request).
+ * A request with sel[i] == 0 is not sent: it takes no bucket position, does not
+ * count against cap, never raises the overflow status, and gets slot[i] =
+ * RL_SLOT_SKIPPED.  The selected requests are grouped by owner, stable, exactly
+ * as rl_route_pack groups a batch.  Info row 0 counts the selected requests
+ * sent and row 3 the selected requests dropped; rows 1-2 and the unsorted bit
+ * still cover the WHOLE batch, skipped requests included, by the argument
+ * above for dropped ones: every owner must derive the same store clock, and the
+ * sender's batch reached those times whether or not a request went out.  With
+ * sel all ones, send, send_info and slot are byte-identical to rl_route_pack's
+ * (the same kernels, a template predicate).  Real slots stay below 2^30
+ * (rl_router_create), so the two codes never collide with one. */
+int rl_route_pack_sel(rl_router* r, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                      const uint32_t* cfg, const uint8_t* sel, rl_route_rec* send, int64_t* send_info,
+                      uint32_t* slot, void* stream);
 
 /* owner: recv[world * cap] (source s's bucket at s * cap) and recv_info (the
  * received info rows, source s's at RL_ROUTE_INFO * s) -> the decision order:
@@ -251,8 +272,58 @@ int rl_refund_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, c
                             const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
                             void* out_stream, void* done_event);
 
+/* Routed AllowAll: rl_allow_all_batch (include/rl_engine.h)
+ * for members whose keys live on different GPUs.  It is two
+ * routed steps, b and b + 1, with a settle on the sender between them and no
+ * host read (shard.RoutedPipeline.allow_all):
+ *   step b      a decide step of the M members, unchanged; its result side is
+ *               issued at once and unpacked into the caller's arrays
+ *   settle      rl_allow_all_settle_device on the unpacked decisions: verdict
+ *               per member, give-back g per member, sel[i] = g[i] > 0
+ *   step b + 1  a refund step of the selection: rl_route_pack_sel with n = g
+ *               and the members' key, ts and cfg, then exchange, merge and
+ *               rl_refund_routed_device, unchanged; unpacked into rollback
+ * Effect on the shared store: a decide step of ALL ranks' members (merged by
+ * arrival order) followed by ONE refund step of all ranks' give-backs (per
+ * target the sum across ranks, rl_refund_routed_device).  The verb is
+ * conservative across ranks as rl_allow_all_batch is within a call: a group
+ * can be denied on another rank's transient take, and is never admitted on
+ * quota a sequential run would not have.
+ * Clock: the give-backs run at the refund step's store clock, which is at
+ * least the latest ts of the decide step on any rank (rl_allow_all_batch runs
+ * them at the member's own clock): a short window can have expired by then, so
+ * RL_REFUND_NOKEY is more common here.
+ * rollback[i]: RL_REFUND_DONE; RL_REFUND_NOKEY; RL_INVALID -- nothing was asked
+ * back, the member was skipped; RL_DROPPED -- the owner's refund bound
+ * (rl_refund_routed_device) was passed: the take is still in place and the
+ * caller re-issues it as a refund step.  The sender cannot drop a give-back: a
+ * selected member held a bucket position in step b (a member dropped there has
+ * g = 0), and the selected members are a subsequence of step b's, so each has
+ * at most the position it had.
+ * rl_stats moves as for the decide step; the tally and the top keys do not.
+ *
+ * rl_allow_all_settle_device: one kernel on `stream`; it uses none of the
+ * engine's streams, scratch or tables and reads only the engine's device
+ * config table (for the algorithm).  Groups as rl_allow_all_batch: member i
+ * starts a group when i == 0 or first[i] != 0; a run longer than
+ * RL_ALLOW_ALL_MAX_GROUP is RL_INVALID.  decision[] holds the unpacked results
+ * of a routed decide step, so a member may be RL_DROPPED.  verdict[i], on every
+ * member of a group, is the most severe decision of the group, RL_INVALID >
+ * RL_DROPPED > RL_ERROR > RL_DENIED > RL_ALLOWED (a byte of 5 or more counts as
+ * RL_INVALID).  RL_DROPPED tells the caller to resubmit the whole group; it
+ * ranks below RL_INVALID because an invalid group can never pass.  g[i] = n[i]
+ * if the verdict is not RL_ALLOWED and the member took something (a bucket
+ * when it allowed, a window counter when it allowed or denied), else 0 -- a
+ * dropped member took nothing, like an error or invalid one.  sel[i] = g[i] >
+ * 0.  All arrays are device memory of m elements; m is at most the engine's
+ * max_batch; RL_EINVAL for a null pointer (m > 0) or a larger m. */
+int rl_allow_all_settle_device(rl_engine* e, size_t m, const uint8_t* first, const uint32_t* cfg_id,
+                               const int64_t* n, const uint8_t* decision, uint8_t* verdict, int64_t* g,
+                               uint8_t* sel, void* stream);
+
 /* sender: back[world * cap] (the result buckets, send layout) -> the caller's
- * order; a dropped request gets decision RL_DROPPED and zeros */
+ * order; a dropped request gets decision RL_DROPPED and zeros; a request that
+ * rl_route_pack_sel skipped gets {RL_INVALID, 0, 0, 0}: nothing was asked */
 int rl_route_unpack(rl_router* r, size_t m, const uint32_t* slot, const rl_route_res* back, uint8_t* decision,
                     int64_t* remaining, int64_t* retry_after_ns, int64_t* reset_at_ns, void* stream);
 
