@@ -1222,6 +1222,10 @@ extern "C" int rl_decide_batch_device(rl_engine* e, size_t m, const uint64_t* ke
     return RL_OK;
 }
 
+int rl::decide_after_stream(rl_engine* e, uint32_t m, const ReqArgs& a, hipStream_t s) {
+    return run_batch(e, m, a, s, false);
+}
+
 extern "C" int rl_decide_routed_device_io(rl_engine* e, size_t m_max, const uint32_t* count,
                                           const rl_route_rec* recv, const uint32_t* order, const int64_t* server_ms,
                                           rl_route_res* res, void* in_stream, void* out_stream) {

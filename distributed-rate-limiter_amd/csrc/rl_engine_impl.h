@@ -211,6 +211,22 @@ struct rl_engine {
         }
     } allow_all;
 
+    // Charge scratch (rl_charge.h): one allocation made by the first call,
+    // sized for rl_charge_max -- n', the ask's row, the decide's row, then the
+    // host form's staging of `charged`.  `ev` is the end of the last call's
+    // finish kernel on its caller's stream: the next call's ask, on `chain`,
+    // waits for it before it writes the scratch again.  It frees itself with
+    // the engine (rl_engine_destroy drains first).
+    struct ChargeState {
+        void* mem = nullptr;
+        hipEvent_t ev = nullptr;
+        uint64_t calls = 0;
+        ~ChargeState() {
+            if (mem) (void)hipFree(mem);
+            if (ev) (void)hipEventDestroy(ev);
+        }
+    } charge;
+
     // The tally's and the top keys' kernels run on the caller's stream and read
     // the feature's own memory: the end of the last such call on each stream
     // one was enqueued on is what drain(), rl_tally_read and rl_hot_read wait
@@ -283,6 +299,12 @@ namespace rl {
 // every queued kernel of the engine has finished (the engine's streams and,
 // through the back_done events, any caller stream a batch was enqueued on)
 int drain(rl_engine* e);
+
+// One decide batch of m <= max_batch requests whose inputs are made on the
+// device by work queued on s: the grouping waits for s, whatever
+// RL_OPT_PIPELINE says of the caller's arrays (Charge's second step,
+// rl_ops.hip).  Otherwise rl_decide_batch_device on one chunk.
+int decide_after_stream(rl_engine* e, uint32_t m, const ReqArgs& a, hipStream_t s);
 
 // slot ids (the sort keys) are 31 bits: token-bucket slots, then window slots,
 // then invalid_key

@@ -4,7 +4,9 @@
 // stream between two replays (chain_op, rl_engine_impl.h).  AllowAll
 // (rl_allow_all.h) composes a decide, its settle kernel on the caller's stream
 // and a refund; the routed AllowAll's settle (rl_allow_all_settle_device) is
-// the second instantiation of that kernel's text.
+// the second instantiation of that kernel's text.  Charge (rl_charge.h)
+// composes its ask as a chain op, a decide and its finish kernel on the
+// caller's stream.
 // A code object of its own: that of the decision kernels (rl_engine.hip) does
 // not change with it.
 #include <hip/hip_runtime.h>
@@ -12,6 +14,7 @@
 #include "../../include/rl_engine.h"
 #include "../../include/rl_route.h"
 #include "rl_allow_all.h"
+#include "rl_charge.h"
 #include "rl_engine_impl.h"
 #include "rl_peek.h"
 #include "rl_refund.h"
@@ -76,6 +79,7 @@ static int run_refund_routed(rl_engine* e, size_t m_max, const RoutedIo& io, hip
                              hipEvent_t done);
 
 static int allow_all_warm_up(rl_engine* e);
+static int charge_warm_up(rl_engine* e);
 
 enum RoutedKind { ROUTED_PEEK, ROUTED_RESET, ROUTED_REFUND };
 
@@ -124,7 +128,8 @@ extern "C" int rl_refund_routed_device(rl_engine* e, size_t m_max, const uint32_
 // rejected: no config is registered yet.  The staging arrays hold zeros.
 // No refund kernel is launched here, routed or not: the first refund of an
 // engine allocates its scratch, and the warm-up allocates nothing.  Last,
-// AllowAll's settle kernel on one member.
+// AllowAll's settle kernel on one member, and Charge's two kernels on one
+// request.
 int rl::ops_warm_up(rl_engine* e) {
     hipStream_t s = e->stream;
     const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
@@ -137,7 +142,9 @@ int rl::ops_warm_up(rl_engine* e) {
     if (r != RL_OK) return r;
     const int rr = run_reset_batch(e, 1, e->d_key, e->d_ts, e->d_cfgid, e->d_dec, s, false);
     if (rr != RL_OK) return rr;
-    return allow_all_warm_up(e);
+    const int ra = allow_all_warm_up(e);
+    if (ra != RL_OK) return ra;
+    return charge_warm_up(e);
 }
 
 int rl::ops_q14_slow(rl_engine* e, unsigned long long* out) {
@@ -476,6 +483,129 @@ extern "C" int rl_allow_all_batch(rl_engine* e, size_t m, const uint64_t* key_id
     if (r != RL_OK) return r;
     HIPCHK(e, hipMemcpyAsync(verdict, B.verdict, m, hipMemcpyDeviceToHost, s));
     if (rollback) HIPCHK(e, hipMemcpyAsync(rollback, B.rollback, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    // the sticky device status, as rl_decide_batch returns it (a full table: RL_ENOMEM)
+    return rl_engine_sync(e);
+}
+
+// --- Charge (rl_charge.h) ----------------------------------------------------
+
+static uint32_t charge_max(const rl_engine* e) { return std::min<uint32_t>(e->max_batch, CHARGE_MAX); }
+
+// the engine's Charge scratch, allocated by the first call: arrays of
+// rl_charge_max elements, the 8-byte ones first
+static int charge_scratch(rl_engine* e, ChargeScratch* out) {
+    auto& A = e->charge;
+    const size_t M = charge_max(e);
+    if (!A.ev) HIPCHK(e, hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
+    if (!A.mem && hipMalloc(&A.mem, M * (7 * sizeof(int64_t) + 2)) != hipSuccess) {
+        A.mem = nullptr;
+        return fail(e, RL_ENOMEM, "Charge scratch: out of device memory");
+    }
+    int64_t* p = (int64_t*)A.mem;
+    out->np = p;
+    out->ask_reset = p + M;
+    out->ask_tok = (double*)(p + 2 * M);
+    out->rem = p + 3 * M;
+    out->retry = p + 4 * M;
+    out->reset = p + 5 * M;
+    out->tok = (double*)(p + 6 * M);
+    out->dec = (uint8_t*)(p + 7 * M);
+    out->kind = out->dec + M;
+    return RL_OK;
+}
+
+static void launch_charge_ask(rl_engine* e, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                              const uint32_t* cfg, const int64_t* sms, const ChargeScratch& S, hipStream_t c) {
+    k_charge_ask<<<grid_for(m, CHARGE_BLOCK, CHARGE_GRID), CHARGE_BLOCK, 0, c>>>(
+        (uint64_t)m, key, ts, n, cfg, sms, e->d_cfg, (uint32_t)e->h_cfg.size(), e->d_tb, e->tb_cap - 1, e->profile, S);
+}
+
+static int launch_charge_finish(rl_engine* e, size_t m, const int64_t* n, const ChargeScratch& S, uint8_t* decision,
+                                int64_t* charged, int64_t* remaining, int64_t* reset, double* tokens, hipStream_t s) {
+    k_charge_finish<<<grid_for(m, CHARGE_BLOCK, CHARGE_GRID), CHARGE_BLOCK, 0, s>>>((uint64_t)m, n, S, decision,
+                                                                                    charged, remaining, reset, tokens);
+    HIPCHK(e, hipGetLastError());
+    return RL_OK;
+}
+
+// One Charge call of 0 < m <= rl_charge_max requests with device pointers: the
+// ask as a chain op ordered like run_peek (s then sees n'), the decide on n' as
+// one batch whose grouping always waits for s -- n' is made on the device,
+// whatever RL_OPT_PIPELINE says of the caller's arrays -- and the finish kernel
+// on s.  The scratch is allocated before anything is enqueued.
+static int run_charge(rl_engine* e, size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n,
+                      const uint32_t* cfg, const int64_t* sms, uint8_t* decision, int64_t* charged,
+                      int64_t* remaining, int64_t* reset, double* tokens, hipStream_t s, bool inputs_ready) {
+    ChargeScratch S;
+    int r = charge_scratch(e, &S);
+    if (r != RL_OK) return r;
+    // the previous call's finish, enqueued on any stream, may still read the
+    // scratch: the ask waits for its end on `chain`, and everything that
+    // writes the scratch in this call comes after the ask
+    if (e->charge.calls) HIPCHK(e, hipStreamWaitEvent(e->chain, e->charge.ev, 0));
+    e->charge.calls++;
+    r = chain_op(e, s, inputs_ready, s, e->ev_peek, nullptr,
+                 [&](hipStream_t c) { launch_charge_ask(e, m, key, ts, n, cfg, sms, S, c); });
+    if (r != RL_OK) return r;
+    const ReqArgs a{key, ts, S.np, cfg, sms, S.dec, S.rem, S.retry, S.reset, S.tok};
+    r = decide_after_stream(e, (uint32_t)m, a, s);
+    if (r == RL_OK) r = launch_charge_finish(e, m, n, S, decision, charged, remaining, reset, tokens, s);
+    // recorded also after a failure: whatever was enqueued on s is before it
+    HIPCHK(e, hipEventRecord(e->charge.ev, s));
+    return r;
+}
+
+// both kernels on one request read from the staging arrays: no config is
+// registered yet, so the request is invalid and no table is read.  The
+// results go to staging words; the scratch stands in the staging arrays too
+// (one element each), so nothing is allocated.
+static int charge_warm_up(rl_engine* e) {
+    const ChargeScratch S{e->d_rem, e->d_reset, e->d_tok, e->d_rem, e->d_retry, e->d_reset, e->d_tok, e->d_dec,
+                          (uint8_t*)e->d_sms};
+    hipStream_t s = e->stream;
+    launch_charge_ask(e, 1, e->d_key, e->d_ts, e->d_n, e->d_cfgid, nullptr, S, s);
+    HIPCHK(e, hipGetLastError());
+    return launch_charge_finish(e, 1, e->d_n, S, e->d_dec, e->d_retry, e->d_rem, e->d_reset, e->d_tok, s);
+}
+
+extern "C" uint32_t rl_charge_max(rl_engine* e) { return e ? charge_max(e) : 0; }
+
+extern "C" int rl_charge_grid_cap(void) { return CHARGE_GRID * CHARGE_BLOCK; }
+
+extern "C" int rl_charge_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                      const int64_t* n, const uint32_t* cfg_id, const int64_t* server_ms,
+                                      uint8_t* decision, int64_t* charged, int64_t* remaining, int64_t* reset_at_ns,
+                                      double* tokens, void* stream) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !decision || !charged || !remaining || !reset_at_ns)))
+        return RL_EINVAL;
+    if (m > charge_max(e)) return fail(e, RL_EINVAL, "Charge call above rl_charge_max");
+    if (m == 0) return RL_OK;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    return run_charge(e, m, key_id, ts_ns, n, cfg_id, server_ms, decision, charged, remaining, reset_at_ns, tokens, s,
+                      (e->flags & RL_OPT_PIPELINE) != 0);
+}
+
+extern "C" int rl_charge_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                               const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* decision, int64_t* charged,
+                               int64_t* remaining, int64_t* reset_at_ns, double* tokens) {
+    if (!e || (m && (!key_id || !ts_ns || !n || !cfg_id || !decision || !charged || !remaining || !reset_at_ns)))
+        return RL_EINVAL;
+    if (m > charge_max(e)) return fail(e, RL_EINVAL, "Charge call above rl_charge_max");
+    if (m == 0) return RL_OK;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    HIPCHK(e, hipMemsetAsync(e->d_eflags, 0, 4, s));
+    // one chunk: m <= max_batch, the size of the host API's staging arrays
+    int r = stage_in(e, 0, (uint32_t)m, key_id, ts_ns, n, cfg_id, server_ms, s);
+    // the staged inputs arrive on s: the ask always waits for them.  `charged`
+    // is staged through the array a decide stages retry_after_ns through
+    if (r == RL_OK)
+        r = run_charge(e, m, e->d_key, e->d_ts, e->d_n, e->d_cfgid, server_ms ? e->d_sms : nullptr, e->d_dec,
+                       e->d_retry, e->d_rem, e->d_reset, tokens ? e->d_tok : nullptr, s, false);
+    if (r == RL_OK) r = stage_out(e, 0, (uint32_t)m, decision, remaining, charged, reset_at_ns, tokens, s);
+    if (r != RL_OK) return r;
     HIPCHK(e, hipStreamSynchronize(s));
     // the sticky device status, as rl_decide_batch returns it (a full table: RL_ENOMEM)
     return rl_engine_sync(e);

@@ -114,6 +114,20 @@ __device__ inline Out peek_sw(const WinState& w, const Spill& S, int64_t t, int6
     return o;
 }
 
+// tokenBucketScript + AllowN without its writes: the script step itself
+// (tb_step) on a local copy of the key's entry, which is then dropped.  The
+// text k_peek and Charge's ask (rl_charge.h, n = 0) share.
+__device__ inline Out peek_tb(const TbEntry* tb, uint64_t tb_mask, uint64_t k, int64_t t, int64_t n, int64_t sms,
+                              const CfgDev& C, int32_t profile) {
+    const uint32_t s = probe_find(tb, tb_mask, k);
+    TbState st{0.0, 0.0, ABSENT};
+    if (s != NO_SLOT) {
+        const TbEntry e = tb[s];   // the 32-byte entry, once
+        st = TbState{e.tok, e.last, e.when};
+    }
+    return tb_step(st, t, n, sms, C, profile);   // the copy is dropped
+}
+
 // One request per thread, grid-stride.  The tables are only read: a key a
 // later batch's grouping is inserting right now (k_probe's CAS,
 // RL_OPT_PIPELINE) reads either as an empty slot or as a key whose entry
@@ -157,13 +171,7 @@ __device__ __forceinline__ void peek_requests(uint64_t m, const ReqArgs& a, cons
             const int64_t sms = RT ? rsms : a.sms ? a.sms[i] : floor_div(t, 1000000LL);
             const CfgDev C = cfgs[c];
             if (C.alg == ALG_TOKEN_BUCKET) {
-                const uint32_t s = probe_find(tb, tb_mask, k);
-                TbState st{0.0, 0.0, ABSENT};
-                if (s != NO_SLOT) {
-                    const TbEntry e = tb[s];   // the 32-byte entry, once
-                    st = TbState{e.tok, e.last, e.when};
-                }
-                o = tb_step(st, t, n, sms, C, profile);   // the copy is dropped
+                o = peek_tb(tb, tb_mask, k, t, n, sms, C, profile);
             } else {
                 const uint32_t s = probe_find(win, win_mask, k);
                 WinState w;

@@ -175,7 +175,8 @@ public:
     // two kernels on the engine's replay stream between two batches.  Behind
     // a successful decide, the tally and then the top keys count the batch on
     // os_, on the arrays the decide used; behind an AllowAll call they count
-    // its members the same way, with the members' own decisions.
+    // its members the same way, with the members' own decisions, and behind a
+    // Charge call its requests, with the asked n and the verb's decisions.
     int engine_call(Op op, size_t m, const Arrays& a) {
         switch (op) {
             case OP_REQ: {
@@ -193,6 +194,13 @@ public:
             case OP_ALLOW_ALL: {
                 int rc = rl_allow_all_batch_device(e_, m, a.key, a.ts, a.n, a.cfg, nullptr, a.head, a.dec, a.rem, a.retry,
                                                    a.reset, nullptr, a.verdict, nullptr, os_);
+                if (rc == RL_OK && tally_) rc = rl_tally_batch_device(e_, m, a.key, a.cfg, a.n, a.dec, os_);
+                if (rc == RL_OK && hot_) rc = rl_hot_batch_device(e_, m, a.key, a.cfg, a.n, a.dec, os_);
+                return rc;
+            }
+            case OP_CHARGE: {
+                int rc = rl_charge_batch_device(e_, m, a.key, a.ts, a.n, a.cfg, nullptr, a.dec, a.retry, a.rem, a.reset,
+                                                nullptr, os_);
                 if (rc == RL_OK && tally_) rc = rl_tally_batch_device(e_, m, a.key, a.cfg, a.n, a.dec, os_);
                 if (rc == RL_OK && hot_) rc = rl_hot_batch_device(e_, m, a.key, a.cfg, a.n, a.dec, os_);
                 return rc;
@@ -466,7 +474,7 @@ private:
 // synchronous host functions (the CPU tests plug the oracle in here)
 class FnBackend : public Backend {
 public:
-    explicit FnBackend(const rl_coalescer_backend& b) : b_(b) {}
+    explicit FnBackend(const BackendFns& b) : b_(b) {}
     int tally_enable(uint32_t key_slots) override {
         const int rc = tally_.enable(key_slots);
         tally_on_ = rc == RL_OK;
@@ -509,6 +517,13 @@ public:
                 if (rc == RL_OK && hot_on_) hot_.add(s.m, s.key, s.cfg, s.n, s.dec);
                 return rc;
             }
+            case OP_CHARGE: {
+                if (!b_.charge) return RL_EINVAL;
+                const int rc = b_.charge(b_.user, s.m, s.key, s.ts, s.n, s.cfg, s.dec, s.retry, s.rem, s.reset);
+                if (rc == RL_OK && tally_on_) tally_.add(s.m, s.key, s.cfg, s.n, s.dec);
+                if (rc == RL_OK && hot_on_) hot_.add(s.m, s.key, s.cfg, s.n, s.dec);
+                return rc;
+            }
             case OP_RESET: return reset_batch(s);
             default: return RL_EINVAL;
         }
@@ -534,7 +549,7 @@ private:
         }
         return RL_OK;
     }
-    rl_coalescer_backend b_;
+    BackendFns b_;
     HostTally tally_;
     bool tally_on_ = false;
     HostHot hot_;
@@ -543,7 +558,7 @@ private:
 };
 
 std::unique_ptr<Backend> make_gpu_backend(rl_engine* e) { return std::unique_ptr<Backend>(new GpuBackend(e)); }
-std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b) {
+std::unique_ptr<Backend> make_fn_backend(const BackendFns& b) {
     return std::unique_ptr<Backend>(new FnBackend(b));
 }
 
@@ -805,9 +820,9 @@ std::vector<BatchTrace> Coalescer::Trace() {
     return out;
 }
 
-rl_coalescer_stats Coalescer::Stats() {
+Counters Coalescer::Stats() {
     std::lock_guard<std::mutex> g(mu_);
-    rl_coalescer_stats r = st_;
+    Counters r = st_;
     r.pending = pending_;
     return r;
 }
@@ -1136,15 +1151,18 @@ extern "C" int rl_coalescer_create(rl_engine* e, const rl_coalescer_opts* opts, 
 
 extern "C" int rl_coalescer_create_with_host_backend(const rl_coalescer_backend* be, const rl_coalescer_opts* opts,
                                                      rl_coalescer** out) {
-    // a caller compiled before `peek` / `reset_batch` / `refund` / `allow_all` were added passes the shorter struct
+    // a caller compiled before `peek` / `reset_batch` / `refund` / `allow_all` / `charge` were added passes the
+    // shorter struct; one with `charge` passes rl_coalescer_backend_charge's size
     if (!be || !out ||
-        (be->struct_size != sizeof(rl_coalescer_backend) && be->struct_size != offsetof(rl_coalescer_backend, peek) &&
+        (be->struct_size != sizeof(rl_coalescer_backend_charge) && be->struct_size != sizeof(rl_coalescer_backend) && be->struct_size != offsetof(rl_coalescer_backend, peek) &&
          be->struct_size != offsetof(rl_coalescer_backend, reset_batch) &&
          be->struct_size != offsetof(rl_coalescer_backend, refund) &&
          be->struct_size != offsetof(rl_coalescer_backend, allow_all)))
         return RL_EINVAL;
-    rl_coalescer_backend b{};
-    memcpy(&b, be, be->struct_size);
+    rlc::BackendFns b{};
+    memcpy(static_cast<rl_coalescer_backend*>(&b), be, std::min<size_t>(be->struct_size, sizeof(rl_coalescer_backend)));
+    if (be->struct_size == sizeof(rl_coalescer_backend_charge))
+        b.charge = reinterpret_cast<const rl_coalescer_backend_charge*>(be)->charge;
     b.struct_size = sizeof b;
     if (!b.batch) return RL_EINVAL;
     return create(rlc::make_fn_backend(b), opts, out);
@@ -1256,6 +1274,19 @@ extern "C" int rl_coalescer_allow_all(rl_coalescer* c, size_t m, const uint64_t*
     return c->c->Wait(t, -1, decision, remaining, retry_after_ns, reset_at_ns, nullptr, nullptr, verdict);
 }
 
+extern "C" int rl_coalescer_charge(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
+                                   const int64_t* n, const uint32_t* cfg_id, int64_t deadline_ns, uint8_t* decision,
+                                   int64_t* charged, int64_t* remaining, int64_t* reset_at_ns) {
+    if (!c) return RL_EINVAL;
+    // one submission is one launch: a larger one is not split (its duplicates would ask against another state)
+    if (m > c->c->MaxBatch()) return RL_EINVAL;
+    uint64_t t;
+    int rc = c->c->Submit(m, key_id, ts_ns, n, cfg_id, &t, deadline_ns, nullptr, rlc::OP_CHARGE);
+    if (rc != RL_OK) return rc;
+    // `charged` travels where a decide's retry_after_ns does
+    return c->c->Wait(t, -1, decision, remaining, charged, reset_at_ns);
+}
+
 extern "C" int rl_coalescer_peek(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns,
                                  const int64_t* n, const uint32_t* cfg_id, uint8_t* decision, int64_t* remaining,
                                  int64_t* retry_after_ns, int64_t* reset_at_ns) {
@@ -1333,6 +1364,16 @@ extern "C" int rl_coalescer_hot(rl_coalescer* c, rl_hot_key* key_out, size_t key
 
 extern "C" int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out) {
     if (!c || !out || out->struct_size < 8) return RL_EINVAL;
-    rlc::copy_out_sized(out, c->c->Stats());
+    // the struct of before Charge, whatever the caller's size: rl_coalescer_get_stats_charge has the rest
+    const rl_coalescer_stats v = c->c->Stats();
+    rlc::copy_out_sized(out, v);
+    return RL_OK;
+}
+
+extern "C" int rl_coalescer_get_stats_charge(rl_coalescer* c, rl_coalescer_stats_charge* out) {
+    if (!c || !out || out->s.struct_size < 8) return RL_EINVAL;
+    rlc::Counters v = c->c->Stats();
+    v.struct_size = (uint32_t)std::min<size_t>(out->s.struct_size, sizeof v);
+    memcpy(out, &v, v.struct_size);
     return RL_OK;
 }

@@ -26,12 +26,24 @@
 
 namespace rlc {
 
-enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_REFUND, OP_ALLOW_ALL, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT, OP_COUNT };
+enum Op : uint8_t { OP_REQ, OP_RESET, OP_PEEK, OP_REFUND, OP_ALLOW_ALL, OP_CHARGE, OP_INFO, OP_GC, OP_SNAPSHOT, OP_RESTORE, OP_TALLY, OP_HOT, OP_COUNT };
+
+// the coalescer's counters and a host backend's functions: the C structs of
+// include/rl_coalescer.h with their trailing Charge members, laid out as
+// rl_coalescer_stats_charge / rl_coalescer_backend_charge
+struct Counters : rl_coalescer_stats {
+    uint64_t charge_launches = 0;
+};
+static_assert(sizeof(Counters) == sizeof(rl_coalescer_stats_charge), "Counters is rl_coalescer_stats_charge");
+struct BackendFns : rl_coalescer_backend {
+    rl_charge_fn charge = nullptr;
+};
+static_assert(sizeof(BackendFns) == sizeof(rl_coalescer_backend_charge), "BackendFns is rl_coalescer_backend_charge");
 
 // What the queue, the launch and the counters do with a submission of each
 // operation: stated once here and read everywhere else (a `switch (op)` stays
 // only where the action itself differs: which backend call runs).
-using StatField = uint64_t rl_coalescer_stats::*;
+using StatField = uint64_t Counters::*;
 struct OpTraits {
     // carries requests through a launch slot (Submit); the others are single
     // table operations, run synchronously on the submitter thread (SubmitOp)
@@ -57,7 +69,7 @@ struct OpTraits {
     bool grouped;
 };
 constexpr StatField NO_STAT = nullptr;
-using St = rl_coalescer_stats;
+using St = Counters;
 constexpr OpTraits OPS[OP_COUNT] = {
     //              batched reads_n results merges splits q_cap  decides batch  max    launches                 completed      keeps_gc grouped
     /* REQ       */ {true,  true,   true,   true,  true,  true,  true,   true,  true,  NO_STAT,                 &St::decided,  false,   false},
@@ -65,6 +77,7 @@ constexpr OpTraits OPS[OP_COUNT] = {
     /* PEEK      */ {true,  true,   true,   false, true,  true,  false,  false, false, NO_STAT,                 &St::peeked,   false,   false},
     /* REFUND    */ {true,  true,   false,  false, false, true,  false,  false, false, &St::refund_launches,    &St::refunds,  false,   false},
     /* ALLOW_ALL */ {true,  true,   true,   false, false, true,  true,   false, false, &St::allow_all_launches, &St::decided,  false,   true},
+    /* CHARGE    */ {true,  true,   true,   false, false, true,  true,   false, false, &St::charge_launches,    &St::decided,  false,   false},
     /* INFO      */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       false,   false},
     /* GC        */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       false,   false},
     /* SNAPSHOT  */ {false, false,  false,  false, false, false, false,  false, false, NO_STAT,                 NO_STAT,       false,   false},
@@ -191,7 +204,8 @@ public:
     // rl_reset_batch_device) and OP_REFUND: one refund call
     // (rl_refund_batch_device), both with the per-request status into s.dec;
     // OP_ALLOW_ALL: one AllowAll call (rl_allow_all_batch_device), s.head in,
-    // s.verdict out beside the decide's results
+    // s.verdict out beside the decide's results; OP_CHARGE: one Charge call
+    // (rl_charge_batch_device), `charged` where a decide's retry_after_ns goes
     virtual int launch(int slot, Slot& s) = 0;
     virtual int wait(int slot, Slot& s) = 0;     // until launch `slot` completed
     // synchronous table operations (the GPU engine drains its batches first)
@@ -214,7 +228,7 @@ public:
 };
 
 std::unique_ptr<Backend> make_gpu_backend(rl_engine* e);
-std::unique_ptr<Backend> make_fn_backend(const rl_coalescer_backend& b);
+std::unique_ptr<Backend> make_fn_backend(const BackendFns& b);
 
 // one submission: its requests (copied) and results, or one table operation
 struct Sub : Arrays {
@@ -270,7 +284,9 @@ public:
     // requests, launched whole and on its own; Wait's `dec` receives the status;
     // or OP_ALLOW_ALL: one AllowAll call of m <= max_batch members in the
     // groups `first` marks, launched whole and on its own, counted like
-    // requests; Wait's `verdict` receives each member's group verdict
+    // requests; Wait's `verdict` receives each member's group verdict; or
+    // OP_CHARGE: one Charge call of m <= max_batch requests, launched whole and
+    // on its own, counted like requests; Wait's `retry` receives `charged`
     int Submit(size_t m, const uint64_t* key, const int64_t* ts, const int64_t* n, const uint32_t* cfg,
                uint64_t* ticket, int64_t deadline = 0, void* tag = nullptr, Op op = OP_REQ,
                const uint8_t* first = nullptr);
@@ -298,7 +314,7 @@ public:
     // info (optional): an OP_INFO / OP_GC result
     int Wait(uint64_t ticket, int64_t timeout_ns, uint8_t* dec, int64_t* rem, int64_t* retry, int64_t* reset,
              int64_t* done_ns = nullptr, rl_table_info* info = nullptr, uint8_t* verdict = nullptr);
-    rl_coalescer_stats Stats();
+    Counters Stats();
     void Shutdown();
     // the trace ring, oldest first (empty unless RL_COALESCER_TRACE is set)
     std::vector<BatchTrace> Trace();
@@ -361,7 +377,7 @@ private:
     int inflight_ = 0, next_slot_ = 0;
     bool stop_ = false, sub_exited_ = false;
     bool sub_idle_ = false;        // the submitter sleeps on cv_sub_ (submit wakes it only then)
-    rl_coalescer_stats st_{};
+    Counters st_{};
     std::vector<BatchTrace> trace_;   // ring of trace_cap_ batches
     size_t trace_cap_ = 0;
     uint64_t done_batches_ = 0;

@@ -79,6 +79,35 @@ Error MetricsDecorator::RefundMany(const Context& ctx, const std::vector<RefundR
     return e;
 }
 
+static uint64_t sat_add(uint64_t a, uint64_t b) { return a + b < a ? UINT64_MAX : a + b; }
+
+Error MetricsDecorator::ChargeMany(const Context& ctx, const std::vector<ChargeRequest>& reqs, int64_t now_ns,
+                                   std::vector<ChargeOutcome>* out) {
+    std::vector<ChargeOutcome> o;
+    Error e = inner_->ChargeMany(ctx, reqs, now_ns, &o);
+    if (e.is != Error::InvalidN) {
+        std::lock_guard<std::mutex> g(mu_);
+        charge_used_ = true;
+        if (!e)
+            for (size_t i = 0; i < reqs.size(); i++) {
+                charged_units_ = sat_add(charged_units_, (uint64_t)o[i].charged);
+                charge_short_units_ = sat_add(charge_short_units_, (uint64_t)(reqs[i].n - o[i].charged));
+            }
+    }
+    if (!e && out) *out = o;
+    return e;
+}
+
+uint64_t MetricsDecorator::ChargedUnits() const {
+    std::lock_guard<std::mutex> g(mu_);
+    return charged_units_;
+}
+
+uint64_t MetricsDecorator::ChargeShortUnits() const {
+    std::lock_guard<std::mutex> g(mu_);
+    return charge_short_units_;
+}
+
 void MetricsDecorator::ObserveAllowAll(const AllowAllEvent& ev) {
     {
         std::lock_guard<std::mutex> g(mu_);
@@ -175,6 +204,18 @@ std::string MetricsDecorator::Expose() const {
                  alg.c_str(), (unsigned long long)rolled_back_units_);
         s += line;
     }
+    if (charge_used_) {
+        s += "# HELP rate_limiter_charged_units_total Units of usage recorded after the fact.\n"
+             "# TYPE rate_limiter_charged_units_total counter\n";
+        snprintf(line, sizeof line, "rate_limiter_charged_units_total{algorithm=\"%s\"} %llu\n", alg.c_str(),
+                 (unsigned long long)charged_units_);
+        s += line;
+        s += "# HELP rate_limiter_charge_short_units_total Units a charge asked for and the limiter could not cover.\n"
+             "# TYPE rate_limiter_charge_short_units_total counter\n";
+        snprintf(line, sizeof line, "rate_limiter_charge_short_units_total{algorithm=\"%s\"} %llu\n", alg.c_str(),
+                 (unsigned long long)charge_short_units_);
+        s += line;
+    }
     return s;
 }
 
@@ -244,6 +285,22 @@ Error LoggingDecorator::RefundMany(const Context& ctx, const std::vector<RefundR
         sink_(LogLevel::Debug, "quota refunded",
               {{"key", reqs[i].key}, {"n", std::to_string(reqs[i].n)}, {"applied", a[i] ? "true" : "false"}});
     if (applied) *applied = a;
+    return e;
+}
+
+Error LoggingDecorator::ChargeMany(const Context& ctx, const std::vector<ChargeRequest>& reqs, int64_t now_ns,
+                                   std::vector<ChargeOutcome>* out) {
+    std::vector<ChargeOutcome> o;
+    Error e = inner_->ChargeMany(ctx, reqs, now_ns, &o);
+    if (e) {
+        sink_(LogLevel::Error, "rate limiter charge error", {{"keys", std::to_string(reqs.size())}, {"error", e.msg}});
+        return e;
+    }
+    for (size_t i = 0; i < reqs.size(); i++)
+        if (o[i].charged < reqs[i].n)
+            sink_(LogLevel::Debug, "charge short",
+                  {{"key", reqs[i].key}, {"n", std::to_string(reqs[i].n)}, {"charged", std::to_string(o[i].charged)}});
+    if (out) *out = o;
     return e;
 }
 

@@ -47,6 +47,12 @@ public:
     // counted under names of their own: refunds by `applied`, refunded units
     Error RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
                      std::vector<uint8_t>* applied) override;
+    // counted under names of their own: the units charged and the units a
+    // charge fell short by (n - charged)
+    Error ChargeMany(const Context& ctx, const std::vector<ChargeRequest>& reqs, int64_t now_ns,
+                     std::vector<ChargeOutcome>* out) override;
+    uint64_t ChargedUnits() const;
+    uint64_t ChargeShortUnits() const;
     void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                     std::vector<BatchOutcome>* out) override;
     const Config& config() const override { return inner_->config(); }
@@ -84,6 +90,9 @@ private:
     uint64_t allow_alls_[2] = {0, 0};   // [0] denied or failed, [1] allowed
     uint64_t rolled_back_units_ = 0;    // saturates
     bool allow_all_used_ = false;
+    uint64_t charged_units_ = 0;        // saturates
+    uint64_t charge_short_units_ = 0;   // saturates
+    bool charge_used_ = false;
 };
 
 enum class LogLevel { Debug = 0, Info = 1, Warn = 2, Error = 3 };
@@ -113,6 +122,10 @@ public:
     // "quota refunded" at Debug per request, "rate limiter refund error" at Error per failed call
     Error RefundMany(const Context& ctx, const std::vector<RefundRequest>& reqs, int64_t now_ns,
                      std::vector<uint8_t>* applied) override;
+    // "charge short" at Debug per request charged less than its n, "rate limiter charge error" at Error per
+    // failed call
+    Error ChargeMany(const Context& ctx, const std::vector<ChargeRequest>& reqs, int64_t now_ns,
+                     std::vector<ChargeOutcome>* out) override;
     void BatchAllow(const Context& ctx, const std::vector<BatchRequest>& reqs,
                     std::vector<BatchOutcome>* out) override;
     const Config& config() const override { return inner_->config(); }

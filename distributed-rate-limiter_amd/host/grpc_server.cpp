@@ -229,9 +229,10 @@ struct Conn;
 // K_PEEK: a read-only AllowN (rl_coalescer_peek); K_RESET_BATCH: many resets, one coalescer submission;
 // K_USAGE: RateLimiterMetrics.Usage, one rl_coalescer_tally; K_TOPKEYS: RateLimiterTopKeys.TopKeys, one
 // rl_coalescer_hot; K_REFUND / K_REFUND_BATCH: RateLimiterRefund, one refund submission (rl_coalescer_refund);
-// K_ALLOW_ALL / K_ALLOW_ALL_BATCH: RateLimiterMulti, one AllowAll submission (rl_coalescer_allow_all)
+// K_ALLOW_ALL / K_ALLOW_ALL_BATCH: RateLimiterMulti, one AllowAll submission (rl_coalescer_allow_all);
+// K_CHARGE / K_CHARGE_BATCH: RateLimiterCharge, one Charge submission (rl_coalescer_charge)
 enum Kind : uint8_t { K_ALLOW, K_BATCH, K_RESET, K_PEEK, K_RESET_BATCH, K_USAGE, K_TOPKEYS, K_REFUND, K_REFUND_BATCH,
-                      K_ALLOW_ALL, K_ALLOW_ALL_BATCH, K_COUNT };
+                      K_ALLOW_ALL, K_ALLOW_ALL_BATCH, K_CHARGE, K_CHARGE_BATCH, K_COUNT };
 
 // What each kind of RPC asks of the coalescer and how it reports, stated once.
 struct KindTraits {
@@ -273,6 +274,10 @@ constexpr KindTraits KINDS[K_COUNT] = {
                           "bad AllowAllRequest", true, false, false},
     /* K_ALLOW_ALL_BATCH */ {rlc::OP_ALLOW_ALL, true, true, "failed to check rate limit: ", nullptr,
                           "bad AllowAllBatchRequest", true, false, false},
+    /* K_CHARGE       */ {rlc::OP_CHARGE, true, true, "failed to charge rate limit: ", nullptr,
+                          nullptr, true, false, false},
+    /* K_CHARGE_BATCH */ {rlc::OP_CHARGE, true, true, "failed to charge rate limit: ", nullptr,
+                          "bad ChargeBatchRequest", true, false, false},
 };
 // a queued read that writes into buffers its Rpc owns: not cancelled when its
 // client goes away, but detached and left to finish
@@ -311,6 +316,7 @@ struct BatchItem {
     std::string name;          // the unknown limiter's name
     std::string key;           // Rpc.named: the key's name (remembered if it is denied or watched)
     uint64_t id = 0;           // Rpc.named: its key id
+    int64_t n = 0;             // K_CHARGE, K_CHARGE_BATCH: the units asked (short = n - charged)
 };
 
 // one request of a RateLimiterMulti RPC: its checks are `checks` entries of
@@ -596,6 +602,37 @@ Outcome decide_outcome(const Limiter* lim, int64_t t, int rc, uint8_t dec, int64
     return o;
 }
 
+// ChargeResponse {charged = 1, short = 2, over_limit = 3, remaining = 4, reset_at_unix_ns = 5, error = 6} of one
+// charge of n units, or the error branch (python/rl_server.py _charge_result).  A storage error: a fail-open
+// limiter answers charged = 0 with no error -- the usage is not recorded and nobody is held up --, a
+// fail-closed one has the error
+struct ChargeOutcome {
+    std::string msg, error;
+    int code = GRPC_OK;
+};
+ChargeOutcome charge_outcome(const Limiter* lim, int64_t t, int rc, uint8_t dec, int64_t n, int64_t charged,
+                             int64_t rem, int64_t reset) {
+    ChargeOutcome o;
+    if (rc == RL_OK && (dec == RL_ALLOWED || dec == RL_DENIED)) {
+        put_int(o.msg, 1, charged);
+        put_int(o.msg, 2, n - charged);
+        put_int(o.msg, 3, dec == RL_DENIED ? 1 : 0);
+        put_int(o.msg, 4, rem);
+        put_int(o.msg, 5, reset);
+        return o;
+    }
+    if (lim->fail_open) {
+        put_int(o.msg, 2, n);
+        put_int(o.msg, 5, lim->fail_open_reset_at(t));
+        return o;
+    }
+    // the error text and status of the decide's error branch, under this verb's prefix
+    const Outcome d = decide_outcome(lim, t, rc, dec, 0, 0, 0);
+    o.code = d.code;
+    o.error = KINDS[K_CHARGE].fail + d.r.error.substr(strlen(KINDS[K_ALLOW].fail));
+    return o;
+}
+
 // the limiter's name of a result row (field 1), by its config id
 void put_limiter_name(std::string& o, const Server* s, uint32_t cfg) {
     for (const Limiter& l : s->lims)
@@ -756,6 +793,15 @@ void finish_rpc(Io* io, Rpc& rpc, int rc, const Results& r = {}) {
             }
             break;
         }
+        case K_CHARGE: {
+            // `charged` travels where a decide's retry_after_ns does
+            const ChargeOutcome o = charge_outcome(rpc.lim, rpc.t, rc, r.dec ? r.dec[0] : 0, rpc.items[0].n,
+                                                   r.retry ? r.retry[0] : 0, r.rem ? r.rem[0] : 0,
+                                                   r.reset ? r.reset[0] : 0);
+            if (o.code != GRPC_OK) return respond_err(c, st, o.code, o.error);
+            msg = o.msg;
+            break;
+        }
         case K_ALLOW:
         case K_PEEK: {
             const Outcome o = allow_outcome(io, rpc, rpc.lim, rpc.id, rpc.key, rc, r, 0);
@@ -780,6 +826,18 @@ void finish_rpc(Io* io, Rpc& rpc, int rc, const Results& r = {}) {
                         if (b.err) res.error = err;
                         else res = allow_outcome(io, rpc, b.lim, b.id, b.key, rc, r, j).r;
                         put_allow_response(one, res);
+                        break;
+                    }
+                    case K_CHARGE_BATCH: {
+                        if (b.err) {
+                            put_bytes(one, 6, err);
+                            break;
+                        }
+                        const ChargeOutcome o = charge_outcome(b.lim, rpc.t, rc, r.dec ? r.dec[j] : 0, b.n,
+                                                               r.retry ? r.retry[j] : 0, r.rem ? r.rem[j] : 0,
+                                                               r.reset ? r.reset[j] : 0);
+                        one = o.msg;
+                        put_bytes(one, 6, o.error);
                         break;
                     }
                     case K_REFUND_BATCH:
@@ -863,7 +921,7 @@ bool parse_top_clear(std::string_view msg, size_t* top, bool* clear) {
     return pb.ok;
 }
 
-// AllowBatch, ResetBatch, RefundBatch: a message of repeated requests (field
+// AllowBatch, ResetBatch, RefundBatch, ChargeBatch: a message of repeated requests (field
 // 1) is one submission of those that can run; the others keep their error
 void dispatch_batch(Conn* c, Stream* st, std::string_view msg, Kind kind) {
     Io* io = c->io;
@@ -894,6 +952,7 @@ void dispatch_batch(Conn* c, Stream* st, std::string_view msg, Kind kind) {
             ts.push_back(k.takes_at && r.at ? r.at - 1 : rpc.t);
             n.push_back(r.n);
             cfg.push_back(it.lim->cfg);
+            it.n = r.n;
             if (rpc.named) {
                 it.key = std::string(r.key);
                 it.id = key.back();
@@ -1002,6 +1061,22 @@ void dispatch(Conn* c, Stream* st) {
     if (p == "/ratelimiter.v1.RateLimiterRefund/RefundBatch") return dispatch_batch(c, st, msg, K_REFUND_BATCH);
     if (p == "/ratelimiter.v1.RateLimiterMulti/AllowAll") return dispatch_allow_all(c, st, msg, K_ALLOW_ALL);
     if (p == "/ratelimiter.v1.RateLimiterMulti/AllowAllBatch") return dispatch_allow_all(c, st, msg, K_ALLOW_ALL_BATCH);
+    if (p == "/ratelimiter.v1.RateLimiterCharge/ChargeBatch") return dispatch_batch(c, st, msg, K_CHARGE_BATCH);
+    if (p == "/ratelimiter.v1.RateLimiterCharge/Charge") {
+        ReqMsg r;
+        if (!parse_req(msg, &r)) return respond_err(c, st, GRPC_INTERNAL, "bad ChargeRequest");
+        const Limiter* lim = s->find(r.limiter);
+        if (!lim) return respond_err(c, st, GRPC_INVALID_ARGUMENT, "unknown limiter " + py_repr(r.limiter));
+        if (r.n <= 0) return respond_err(c, st, GRPC_INVALID_ARGUMENT, ERR_INVALID_N);
+        const int64_t now = s->now();
+        const uint64_t id = s->key_id(lim, r.key);
+        const int64_t n = r.n;
+        const uint32_t cfg = lim->cfg;
+        Rpc rpc{c, st->id, K_CHARGE, now, 0, lim, {}, 1};
+        rpc.items.push_back(BatchItem{lim, 0, {}});
+        rpc.items[0].n = n;
+        return submit_rpc(io, st, std::move(rpc), &id, &now, &n, &cfg);
+    }
     if (p == "/ratelimiter.v1.RateLimiterRefund/Refund") {
         ReqMsg r;
         if (!parse_req(msg, &r)) return respond_err(c, st, GRPC_INTERNAL, "bad RefundRequest");

@@ -404,6 +404,60 @@ public:
         return Error{};
     }
 
+    Error ChargeMany(const Context& ctx, const std::vector<ChargeRequest>& reqs, int64_t now_ns,
+                     std::vector<ChargeOutcome>* out) override {
+        const size_t m = reqs.size();
+        for (const auto& r : reqs)
+            if (r.n <= 0) return ErrInvalidN;
+        if (out) out->assign(m, ChargeOutcome{});
+        if (m == 0) return Error{};
+        const int64_t now = now_ns == INT64_MIN ? eng_->clock() : now_ns;
+        const int64_t clock = eng_->server_ms_override != INT64_MIN ? eng_->server_ms_override
+                                                                    : rl::floor_div(now, 1000000LL);
+        std::vector<uint8_t> dec(m, rl::DEC_INVALID);
+        std::vector<int64_t> got(m), rem(m), reset(m);
+        std::string cause;
+        int rc = RL_OK;
+        if (closed_.load()) {
+            cause = "engine: client is closed";
+            rc = RL_EINVAL;
+        } else if (ctx.cancelled.load()) {
+            cause = "context canceled";
+            rc = RL_EINVAL;
+        } else if (ctx.deadline_ns && eng_->clock() >= ctx.deadline_ns) {
+            cause = "context deadline exceeded";
+            rc = RL_EINVAL;
+        } else {
+            std::vector<uint64_t> id(m);
+            std::vector<int64_t> n(m);
+            for (size_t i = 0; i < m; i++) {
+                id[i] = eng_->Intern(cfg_.FormatKey(reqs[i].key));   // a charge inserts its key, as AllowN does
+                n[i] = reqs[i].n;
+            }
+            const std::vector<int64_t> ts(m, now), sms(m, clock);
+            const std::vector<uint32_t> cfg(m, cfg_id_);
+            std::lock_guard<std::mutex> g(eng_->mu());
+            rc = rl_charge_batch(eng_->raw(), m, id.data(), ts.data(), n.data(), cfg.data(), sms.data(), dec.data(),
+                                 got.data(), rem.data(), reset.data(), nullptr);
+            if (rc != RL_OK) cause = engine_error(eng_->raw(), rc);
+        }
+        for (size_t i = 0; i < m; i++) {
+            if (rc == RL_OK && (dec[i] == rl::DEC_ALLOWED || dec[i] == rl::DEC_DENIED)) {
+                if (out) (*out)[i] = ChargeOutcome{got[i], dec[i] == rl::DEC_DENIED, rem[i], reset[i]};
+                continue;
+            }
+            if (cfg_.FailOpen) {   // not recorded, and nobody is held up
+                if (out) (*out)[i] = ChargeOutcome{0, false, 0, fail_open_reset_at(now)};
+                continue;
+            }
+            const std::string why = rc != RL_OK ? cause
+                                    : dec[i] == rl::DEC_ERROR ? "ERR increment or decrement would overflow"
+                                                              : "engine rejected the request";
+            return Error::New(Error::Other, "failed to charge rate limit: " + why);
+        }
+        return Error{};
+    }
+
     Error Close() override {
         closed_.store(true);
         return Error{};
@@ -919,6 +973,37 @@ extern "C" int rll_refund_n(rll_limiter* l, const char* key, size_t keylen, int6
                             uint8_t* applied, char* err, size_t errlen) {
     if (!l || (!key && keylen)) return RLL_ERR_ARG;
     return rll_refund_many(l, 1, &key, &keylen, &n, &at_ns, now_ns, applied, err, errlen);
+}
+
+extern "C" int rll_charge_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens,
+                               const int64_t* n, int64_t now_ns, int ctx_cancelled, rll_charge* out, char* err,
+                               size_t errlen) {
+    if (!l || (m && (!keys || !keylens || !n || !out))) return RLL_ERR_ARG;
+    for (size_t i = 0; i < m; i++)
+        if (!keys[i] && keylens[i]) return RLL_ERR_ARG;
+    std::vector<ChargeRequest> reqs(m);
+    for (size_t i = 0; i < m; i++) {
+        reqs[i].key.assign(keys[i] ? keys[i] : "", keylens[i]);
+        reqs[i].n = n[i];
+    }
+    Context ctx;
+    ctx.cancelled.store(ctx_cancelled != 0);
+    std::vector<ChargeOutcome> o;
+    const Error e = l->lim->ChargeMany(ctx, reqs, now_ns == RLL_NOW_WALL ? INT64_MIN : now_ns, &o);
+    if (e) {
+        put_err(err, errlen, e.msg);
+        return e.is == Error::InvalidN ? RLL_ERR_INVALID_N : RLL_ERR_CHARGE;
+    }
+    for (size_t i = 0; i < m; i++)
+        out[i] = rll_charge{o[i].charged, n[i] - o[i].charged, o[i].remaining, o[i].reset_at,
+                            (uint8_t)(o[i].over_limit ? 1 : 0), {0, 0, 0, 0, 0, 0, 0}};
+    return RLL_OK;
+}
+
+extern "C" int rll_charge_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int64_t now_ns,
+                            int ctx_cancelled, rll_charge* out, char* err, size_t errlen) {
+    if (!l || (!key && keylen) || !out) return RLL_ERR_ARG;
+    return rll_charge_many(l, 1, &key, &keylen, &n, now_ns, ctx_cancelled, out, err, errlen);
 }
 
 extern "C" int rll_allow_all(rll_limiter* const* ls, size_t k, const char* const* keys, const size_t* keylens,

@@ -146,6 +146,21 @@ struct RefundRequest {
     int64_t at_ns = 0;
 };
 
+// one charge: n units of usage, known after the fact, recorded against `key`
+struct ChargeRequest {
+    std::string key;
+    int64_t n = 1;
+};
+// what became of it: `charged` units were recorded (a bucket gives up what it
+// holds, a window counter records all of n); `over_limit`: less than n was
+// charged, or the window's count is now above its limit
+struct ChargeOutcome {
+    int64_t charged = 0;
+    bool over_limit = false;
+    int64_t remaining = 0;
+    int64_t reset_at = 0;        // Unix ns
+};
+
 class Engine;
 // a limiter's member of an AllowAll group (RateLimiter::AllowAllMemberOf)
 struct AllowAllMember {
@@ -204,6 +219,28 @@ public:
         std::vector<uint8_t> a;
         Error e = RefundMany(ctx, {RefundRequest{key, n, at_ns}}, now_ns, &a);
         if (!e && applied) *applied = a[0] != 0;
+        return e;
+    }
+    // Charge (new; rl_charge_batch): record usage that is only known after
+    // the fact, every request of the call in ONE engine call.  A token bucket
+    // gives up min(n, what it holds) and never goes below zero; a window
+    // counter records the whole n, over its limit or not.  Within one call a
+    // later request for the same bucket asks against the state before the
+    // call, so it can charge 0 where a call of its own would charge the rest:
+    // its outcome says so, and the caller charges again.  now_ns (INT64_MIN:
+    // the engine clock) is the time of every request.  Any n <= 0 is
+    // ErrInvalidN before any I/O.  A storage error (closed limiter, cancelled
+    // context, engine failure, a request the engine could not execute): a
+    // fail-open limiter answers charged = 0 with no error -- the usage is not
+    // recorded and the caller is not held up --, a fail-closed one returns
+    // "failed to charge rate limit: ...".
+    virtual Error ChargeMany(const Context& ctx, const std::vector<ChargeRequest>& reqs, int64_t now_ns,
+                             std::vector<ChargeOutcome>* out) = 0;
+    // one charge (a call of one)
+    Error ChargeN(const Context& ctx, const std::string& key, int64_t n, int64_t now_ns, ChargeOutcome* out) {
+        std::vector<ChargeOutcome> o;
+        Error e = ChargeMany(ctx, {ChargeRequest{key, n}}, now_ns, &o);
+        if (!e && out) *out = o[0];
         return e;
     }
     // AllowAll (new; ratelimiter::AllowAll below): this limiter's member of a

@@ -36,6 +36,7 @@ KEY_RESERVED = (1 << 64) - 1
 
 RLL_OK, RLL_ERR_INVALID_N, RLL_ERR_FAILED, RLL_ERR_CONFIG, RLL_ERR_RESET, RLL_ERR_ARG = 0, 1, 2, 3, 4, 5
 RLL_ERR_REFUND = 6
+RLL_ERR_CHARGE = 7
 NOW_WALL = -(1 << 63)
 SMS_DEFAULT = -(1 << 63)
 
@@ -45,6 +46,18 @@ class _Sized(C.Structure):
 
     def __init__(self, *args, **kw):
         super().__init__(C.sizeof(self), *args, **kw)
+
+
+class rll_charge(C.Structure):
+    """rll_charge (include/rl_limiter.h): what became of one charge"""
+    _fields_ = [
+        ("charged", C.c_int64),
+        ("short_by", C.c_int64),
+        ("remaining", C.c_int64),
+        ("reset_at_unix_ns", C.c_int64),
+        ("over_limit", C.c_uint8),
+        ("pad_", C.c_uint8 * 7),
+    ]
 
 
 class rl_opts(_Sized):
@@ -172,6 +185,13 @@ class rl_coalescer_stats(_Sized):
                                   "allow_all_launches")]
 
 
+class rl_coalescer_stats_charge(_Sized):
+    """rl_coalescer_stats_charge (include/rl_coalescer.h): rl_coalescer_stats
+    with Charge's trailing counter.  rl_coalescer_stats above is the struct up
+    to allow_all_launches, as a caller compiled before Charge passes it."""
+    _fields_ = rl_coalescer_stats._fields_ + [("charge_launches", C.c_uint64)]
+
+
 vp = C.c_void_p
 # rl_batch_fn (include/rl_coalescer.h)
 BATCH_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp)
@@ -179,6 +199,7 @@ RESET_FN = C.CFUNCTYPE(C.c_int, vp, C.c_uint32, C.c_uint64, C.c_int64)
 RESET_BATCH_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp)
 REFUND_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp)
 ALLOW_ALL_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp)
+CHARGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp)
 INFO_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.POINTER(rl_table_info))
 GC_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(rl_table_info))
 
@@ -187,6 +208,14 @@ class rl_coalescer_backend(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("batch", BATCH_FN), ("reset", RESET_FN), ("table_info", INFO_FN),
                 ("gc", GC_FN), ("user", vp), ("peek", BATCH_FN), ("reset_batch", RESET_BATCH_FN),
                 ("refund", REFUND_FN), ("allow_all", ALLOW_ALL_FN)]
+
+
+
+class rl_coalescer_backend_charge(_Sized):
+    """rl_coalescer_backend_charge: rl_coalescer_backend with Charge's trailing
+    function"""
+    _fields_ = rl_coalescer_backend._fields_ + [("charge", CHARGE_FN)]
+
 
 _sig = {
     "rl_engine_create": (C.c_int, [C.POINTER(rl_opts), C.POINTER(vp)]),
@@ -211,6 +240,10 @@ _sig = {
     "rl_allow_all_batch_device": (C.c_int, [vp, C.c_size_t] + [vp] * 14),
     "rl_allow_all_max": (C.c_uint32, [vp]),
     "rl_allow_all_grid_cap": (C.c_int, []),
+    "rl_charge_batch": (C.c_int, [vp, C.c_size_t] + [vp] * 10),
+    "rl_charge_batch_device": (C.c_int, [vp, C.c_size_t] + [vp] * 11),
+    "rl_charge_max": (C.c_uint32, [vp]),
+    "rl_charge_grid_cap": (C.c_int, []),
     "rl_tally_enable": (C.c_int, [vp, C.POINTER(rl_tally_opts)]),
     "rl_tally_batch_device": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
     "rl_tally_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
@@ -265,6 +298,8 @@ _sig = {
     "rll_reset_many": (C.c_int, [vp, C.c_size_t, vp, vp, C.c_int64, C.c_char_p, C.c_size_t]),
     "rll_refund_n": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, vp, C.c_char_p,
                                C.c_size_t]),
+    "rll_charge_n": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int, vp, C.c_char_p, C.c_size_t]),
+    "rll_charge_many": (C.c_int, [vp, C.c_size_t, vp, vp, vp, C.c_int64, C.c_int, vp, C.c_char_p, C.c_size_t]),
     "rll_allow_all": (C.c_int, [vp, C.c_size_t, vp, vp, vp, C.c_int64, C.c_int, vp, vp, vp, C.c_char_p, C.c_size_t]),
     "rll_refund_many": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, C.c_int64, vp, C.c_char_p, C.c_size_t]),
     "rll_close": (C.c_int, [vp]),
@@ -281,7 +316,8 @@ _sig = {
     "rl_coalescer_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "rl_coalescer_create_with_backend": (C.c_int, [BATCH_FN, vp, vp, C.POINTER(vp)]),
     "rl_coalescer_create_with_backends": (C.c_int, [BATCH_FN, RESET_FN, vp, vp, C.POINTER(vp)]),
-    "rl_coalescer_create_with_host_backend": (C.c_int, [C.POINTER(rl_coalescer_backend), vp, C.POINTER(vp)]),
+    # the backend by address: rl_coalescer_backend or rl_coalescer_backend_charge, told apart by struct_size
+    "rl_coalescer_create_with_host_backend": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "rl_coalescer_reset": (C.c_int, [vp, C.c_uint64, C.c_int64, C.c_uint32]),
     "rl_coalescer_reset_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp]),
     "rl_coalescer_refund": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, vp]),
@@ -299,6 +335,8 @@ _sig = {
     "rl_coalescer_wait": (C.c_int, [vp, C.c_uint64, C.c_int64, vp, vp, vp, vp]),
     "rl_coalescer_decide": (C.c_int, [vp, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, vp, vp, vp, vp]),
     "rl_coalescer_get_stats": (C.c_int, [vp, C.POINTER(rl_coalescer_stats)]),
+    "rl_coalescer_get_stats_charge": (C.c_int, [vp, C.POINTER(rl_coalescer_stats_charge)]),
+    "rl_coalescer_charge": (C.c_int, [vp, C.c_size_t, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp]),
     "rl_hash_keys_device": (C.c_int, [C.c_size_t, vp, C.c_uint64, vp, C.c_uint64, C.c_char_p, C.c_size_t, vp, vp]),
     "rl_decide_batch_keys_device": (C.c_int, [vp, C.c_size_t, vp, C.c_uint64, vp, C.c_uint64, C.c_char_p,
                                               C.c_size_t] + [vp] * 10),
@@ -354,6 +392,16 @@ class Decisions:
     tokens: np.ndarray | None
 
 
+@dataclass
+class Charges:
+    """rl_charge_batch: one row per request (no retry-after: nothing is retried)"""
+    decision: np.ndarray
+    charged: np.ndarray
+    remaining: np.ndarray
+    reset_at_ns: np.ndarray
+    tokens: np.ndarray | None
+
+
 # rl_opts.flags (include/rl_engine.h)
 OPT_PIPELINE = 1
 # requests one k_peek launch covers at one request per thread (grid cap x block size)
@@ -364,6 +412,8 @@ RESET_GRID_CAP = lib.rl_reset_grid_cap()
 REFUND_GRID_CAP = lib.rl_refund_grid_cap()
 # the same of k_allow_all_settle
 ALLOW_ALL_GRID_CAP = lib.rl_allow_all_grid_cap()
+# the same of k_charge_ask / k_charge_finish
+CHARGE_GRID_CAP = lib.rl_charge_grid_cap()
 # the largest group of an AllowAll call (RL_ALLOW_ALL_MAX_GROUP)
 ALLOW_ALL_MAX_GROUP = 16
 # the same of k_tally
@@ -640,6 +690,38 @@ class Engine:
 
     def allow_all_max(self) -> int:
         return lib.rl_allow_all_max(self.h)
+
+    def charge(self, key, ts, n, cfg, server_ms=None, want_tokens=True, check=True) -> "Charges":
+        """rl_charge_batch: record usage after the fact.  A token bucket gives
+        up min(n, what it holds); a window counter records the whole n.  ->
+        Charges: `decision` (ALLOWED: all of n was charged; DENIED: a bucket
+        charged less than n, or a window is now over its limit), `charged`,
+        `remaining`, `reset_at_ns`, `tokens`"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        sms = None if server_ms is None else np.ascontiguousarray(server_ms, dtype=np.int64)
+        m = key.size
+        assert ts.size == m and n.size == m and cfg.size == m and (sms is None or sms.size == m)
+        out = Charges(np.empty(m, np.uint8), np.empty(m, np.int64), np.empty(m, np.int64), np.empty(m, np.int64),
+                      np.empty(m, np.float64) if want_tokens else None)
+        rc = lib.rl_charge_batch(self.h, m, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), _ptr(sms), _ptr(out.decision),
+                                 _ptr(out.charged), _ptr(out.remaining), _ptr(out.reset_at_ns), _ptr(out.tokens))
+        if check and rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        out.status = rc
+        return out
+
+    def charge_device(self, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, charged_p, rem_p, reset_p, tok_p=None,
+                      stream=None):
+        rc = lib.rl_charge_batch_device(self.h, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, charged_p, rem_p, reset_p,
+                                        tok_p, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def charge_max(self) -> int:
+        return lib.rl_charge_max(self.h)
 
     def allow_all_settle(self, m, first_p, cfg_p, n_p, dec_p, verdict_p, g_p, sel_p, stream=None):
         """rl_allow_all_settle_device (include/rl_route.h): the sender's settle
@@ -980,6 +1062,17 @@ class Result:
     ResetAt: int
 
 
+@dataclass
+class Charge:
+    """rll_charge: `charged` of the n units were recorded, `short` were not;
+    over_limit: a bucket charged less than n, or a window is over its limit"""
+    charged: int
+    short: int
+    over_limit: bool
+    remaining: int
+    reset_at_ns: int
+
+
 class GoError(Exception):
     def __init__(self, code, msg):
         super().__init__(msg)
@@ -1149,6 +1242,30 @@ class RateLimiter:
             return applied.astype(bool), None, rc
         return None, buf.value.decode(), rc
 
+    def charge_n(self, key, n=1, now_ns=NOW_WALL, cancelled=False):
+        """rll_charge_n: record n units of usage after the fact -> (Charge |
+        None, error message | None, code)"""
+        got, err, rc = self.charge_many([key], [n], now_ns, cancelled)
+        return (got[0] if got else None), err, rc
+
+    def charge_many(self, keys, n, now_ns=NOW_WALL, cancelled=False):
+        """rll_charge_many: m charges in ONE engine call, all at now_ns ->
+        ([Charge] | None, error message | None, code)"""
+        m = len(keys)
+        kbs = [k.encode() for k in keys]
+        arr = (C.c_char_p * m)(*kbs)
+        lens = np.array([len(k) for k in kbs], np.uint64)
+        nn = np.ascontiguousarray(n, np.int64)
+        assert nn.size == m
+        out = (rll_charge * max(m, 1))()
+        buf = C.create_string_buffer(512)
+        rc = lib.rll_charge_many(self.h, m, C.cast(arr, vp), _ptr(lens), _ptr(nn), now_ns, 1 if cancelled else 0,
+                                 C.cast(out, vp), buf, 512)
+        if rc != RLL_OK:
+            return None, buf.value.decode(), rc
+        return [Charge(o.charged, o.short_by, bool(o.over_limit), o.remaining, o.reset_at_unix_ns)
+                for o in out[:m]], None, rc
+
     @staticmethod
     def allow_all(checks, now_ns=NOW_WALL, cancelled=False):
         """rll_allow_all: one request against several limiters of one
@@ -1206,8 +1323,8 @@ class Coalescer:
     into engine batches.  `engine` is an Engine (GPU) or, for the CPU tests of
     the batching logic, a Python function with rl_decide_batch's host-array
     signature (the test seam rl_coalescer_create_with_host_backend; `reset`,
-    `table_info`, `gc`, `peek`, `reset_batch`, `refund`, `allow_all`: the other backend
-    functions, optional).
+    `table_info`, `gc`, `peek`, `reset_batch`, `refund`, `allow_all`, `charge`: the
+    other backend functions, optional).
 
     gc_interval_ns > 0 turns on the automatic table GC (rl_coalescer_opts);
     tally_key_slots the usage tally; hot_min (with hot_width, hot_key_slots,
@@ -1216,7 +1333,7 @@ class Coalescer:
     def __init__(self, engine, max_batch=65536, max_in_flight=3, linger_ns=0, queue_cap=0, reset=None,
                  table_info=None, gc=None, peek=None, gc_interval_ns=0, gc_high_pct=0, gc_margin_ms=0,
                  gc_max_tb_capacity=0, gc_max_win_capacity=0, reset_batch=None, tally_key_slots=0, hot_min=0,
-                 hot_width=0, hot_key_slots=0, hot_weight=HOT_REQUESTS, refund=None, allow_all=None):
+                 hot_width=0, hot_key_slots=0, hot_weight=HOT_REQUESTS, refund=None, allow_all=None, charge=None):
         o = rl_coalescer_opts_hot(hot_min=hot_min, hot_width=hot_width, hot_key_slots=hot_key_slots, hot_weight=hot_weight,
                               max_batch=max_batch, max_in_flight=max_in_flight, gc_high_pct=gc_high_pct,
                               linger_ns=linger_ns, queue_cap=queue_cap, gc_interval_ns=gc_interval_ns,
@@ -1228,7 +1345,8 @@ class Coalescer:
             self._be = None
         else:
             # the callbacks live as long as the coalescer
-            self._be = rl_coalescer_backend(
+            self._be = (rl_coalescer_backend_charge if charge else rl_coalescer_backend)(
+                **({"charge": CHARGE_FN(charge)} if charge else {}),
                 batch=BATCH_FN(engine), reset=RESET_FN(reset) if reset else C.cast(None, RESET_FN),
                 table_info=INFO_FN(table_info) if table_info else C.cast(None, INFO_FN),
                 gc=GC_FN(gc) if gc else C.cast(None, GC_FN), user=None,
@@ -1314,6 +1432,21 @@ class Coalescer:
                                         *[_ptr(x) for x in out])
         return rc, out
 
+    def charge(self, key, ts, n, cfg, deadline_ns=0):
+        """rl_coalescer_charge: one Charge call as one submission in sequence
+        order, one launch, never merged or split; blocks until applied.
+        -> (rc, (decision, charged, remaining, reset_at_ns))"""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ts = np.ascontiguousarray(ts, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        cfg = np.ascontiguousarray(cfg, dtype=np.uint32)
+        m = key.size
+        assert ts.size == m and n.size == m and cfg.size == m
+        out = (np.empty(m, np.uint8), np.empty(m, np.int64), np.empty(m, np.int64), np.empty(m, np.int64))
+        rc = lib.rl_coalescer_charge(self.h, m, _ptr(key), _ptr(ts), _ptr(n), _ptr(cfg), deadline_ns,
+                                     *[_ptr(x) for x in out])
+        return rc, out
+
     def peek(self, key, ts, n, cfg):
         """rl_coalescer_peek: read-only queries in sequence order; blocks.
         -> (rc, (decision, remaining, retry_after_ns, reset_at_ns))"""
@@ -1379,6 +1512,12 @@ class Coalescer:
     def stats(self) -> rl_coalescer_stats:
         st = rl_coalescer_stats()
         lib.rl_coalescer_get_stats(self.h, C.byref(st))
+        return st
+
+    def stats_charge(self) -> rl_coalescer_stats_charge:
+        """rl_coalescer_get_stats_charge: the same counters and charge_launches"""
+        st = rl_coalescer_stats_charge()
+        lib.rl_coalescer_get_stats_charge(self.h, C.byref(st))
         return st
 
     def close(self):

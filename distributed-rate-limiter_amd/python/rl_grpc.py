@@ -288,3 +288,23 @@ def top_keys(stub, top: int = 0, clear: bool = False, **kw):
 
 def health_stub(channel):
     return Stub(channel, api("health.proto"), "Health")
+
+
+def charge_stub(channel):
+    """the charge service (RateLimiterCharge: Charge, ChargeBatch)"""
+    return Stub(channel, api("ratelimiter.proto"), "RateLimiterCharge")
+
+
+def charge(stub, limiter: str, key: str, n: int = 1, **kw):
+    """RateLimiterCharge.Charge (stub: charge_stub(channel)): record n units of usage after the fact ->
+    ChargeResponse (charged, short = n - charged, over_limit, remaining, reset_at_unix_ns)"""
+    a = api("ratelimiter.proto")
+    return stub.Charge(a.ChargeRequest(limiter=limiter, key=key, n=n), **kw)
+
+
+def charge_batch(stub, items, **kw):
+    """RateLimiterCharge.ChargeBatch of (limiter, key, n) tuples: one engine call -> [ChargeResponse], each
+    with its own `error` ("" = done)"""
+    a = api("ratelimiter.proto")
+    req = a.ChargeBatchRequest(requests=[a.ChargeRequest(limiter=i[0], key=i[1], n=i[2]) for i in items])
+    return list(stub.ChargeBatch(req, **kw).results)

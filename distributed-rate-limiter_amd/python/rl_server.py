@@ -456,6 +456,74 @@ class RateLimiterService:
         out = self._allow_all([list(r.checks) for r in req.requests], ctx)
         return self.a.AllowAllBatchResponse(responses=[res for _, _, res in out])
 
+    # --- RateLimiterCharge: usage recorded after the fact ---
+
+    def _charge_result(self, lim, t, rc, n, dec, charged, rem, reset):
+        """ChargeResponse, or (None, fail-closed error text, gRPC code).  A
+        storage error: a fail-open limiter answers charged = 0 with no error
+        (the usage is not recorded and nobody is held up)"""
+        if rc == rl_amd.RL_OK and dec in (rl_amd.ALLOWED, rl_amd.DENIED):
+            return self.a.ChargeResponse(charged=charged, short=n - charged, over_limit=dec == rl_amd.DENIED,
+                                         remaining=rem, reset_at_unix_ns=reset), None, None
+        if lim.fail_open:
+            return self.a.ChargeResponse(charged=0, short=n, over_limit=False, remaining=0,
+                                         reset_at_unix_ns=reset_at_ns(lim.alg, lim.limit, lim.window_ns, t)), None, None
+        if rc in self._CTX_ERR:
+            err, code = self._CTX_ERR[rc]
+        else:
+            err = f"engine status {rc}" if rc != rl_amd.RL_OK else "script error (INCRBY overflow)"
+            code = grpc.StatusCode.UNAVAILABLE
+        return None, f"failed to charge rate limit: {err}", code
+
+    def Charge(self, req, ctx):
+        """record n units of usage after the fact (rl_coalescer_charge): one
+        submission, applied in sequence order"""
+        lim = self.by_name.get(req.limiter)
+        if lim is None:
+            ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, f"unknown limiter {req.limiter!r}")
+        if req.n <= 0:
+            ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, ERR_INVALID_N)
+        t = self.clock()
+        rc, (dec, charged, rem, reset) = self.co.charge([self._key_id(lim, req.key)], [t], [req.n], [lim.cfg_id],
+                                                        deadline_ns=self._deadline(ctx))
+        res, err, code = self._charge_result(lim, t, rc, req.n, int(dec[0]), int(charged[0]), int(rem[0]),
+                                             int(reset[0]))
+        if err:
+            ctx.abort(code, err)
+        return res
+
+    def ChargeBatch(self, req, ctx):
+        """many charges: one Charge submission to the coalescer (one engine
+        call); an unknown limiter or n <= 0 is that entry's error string"""
+        rs = req.requests
+        t = self.clock()
+        out = [None] * len(rs)
+        idx, keys, cfg, ns = [], [], [], []
+        groups = {}
+        for i, r in enumerate(rs):
+            lim = self.by_name.get(r.limiter)
+            if lim is None:
+                out[i] = self.a.ChargeResponse(error=f"unknown limiter {r.limiter!r}")
+            elif r.n <= 0:
+                out[i] = self.a.ChargeResponse(error=ERR_INVALID_N)
+            else:
+                groups.setdefault(r.limiter, []).append(len(idx))
+                idx.append(i)
+                keys.append(r.key.encode())
+                cfg.append(lim.cfg_id)
+                ns.append(r.n)
+        if idx:
+            kid = np.empty(len(idx), np.uint64)
+            for name, pos in groups.items():
+                kid[pos] = self._ids(self.by_name[name], [keys[p] for p in pos], len(pos))
+            rc, (dec, charged, rem, reset) = self.co.charge(kid, np.full(len(idx), t, np.int64), np.array(ns, np.int64),
+                                                            np.array(cfg, np.uint32), deadline_ns=self._deadline(ctx))
+            for j, i in enumerate(idx):
+                res, err, _ = self._charge_result(self.by_name[rs[i].limiter], t, rc, ns[j], int(dec[j]),
+                                                  int(charged[j]), int(rem[j]), int(reset[j]))
+                out[i] = res if res is not None else self.a.ChargeResponse(error=err)
+        return self.a.ChargeBatchResponse(results=out)
+
     def AllowBatch(self, req, ctx):
         """many AllowN calls: one submission to the coalescer (one GPU batch
         when it fits); per-request errors in AllowResponse.error"""
@@ -505,7 +573,7 @@ def build_server(service: RateLimiterService, address: str, workers: int = 64) -
     for a, sname, impl in ((service.a, "RateLimiter", service), (service.a, "RateLimiterStatus", service),
                            (service.a, "RateLimiterAdmin", service), (service.a, "RateLimiterMetrics", service),
                            (service.a, "RateLimiterTopKeys", service), (service.a, "RateLimiterRefund", service),
-                           (service.a, "RateLimiterMulti", service),
+                           (service.a, "RateLimiterMulti", service), (service.a, "RateLimiterCharge", service),
                            (service.h, "Health", service)):
         handlers = {}
         for mname, inp, out in a.services[sname]:

@@ -129,6 +129,17 @@ typedef struct rl_coalescer_stats {
     uint64_t allow_all_launches; /* AllowAll submissions launched: one launch each, never merged; not in batches */
 } rl_coalescer_stats;
 
+/* rl_coalescer_stats with Charge's trailing counter, filled in by
+ * rl_coalescer_get_stats_charge: the caller sets s.struct_size to sizeof the
+ * whole struct.  rl_coalescer_get_stats keeps writing rl_coalescer_stats as it
+ * stands above and no more, whatever size a caller passes: callers compiled
+ * against it rely on the size it reports. */
+typedef struct rl_coalescer_stats_charge {
+    rl_coalescer_stats s;
+    uint64_t charge_launches;    /* Charge submissions launched (rl_coalescer_charge): one launch each, never
+                                    merged; not in batches.  Their requests count in submitted / decided */
+} rl_coalescer_stats_charge;
+
 /* Signature of rl_decide_batch (host arrays, synchronous).  A backend of this
  * type replaces the GPU in rl_coalescer_create_with_backend: the CPU tests
  * use it to check the batching and ordering logic on hosts without a GPU. */
@@ -149,6 +160,10 @@ typedef int (*rl_refund_fn)(void* user, size_t m, const uint64_t* key_id, const 
 typedef int (*rl_allow_all_fn)(void* user, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
                                const uint32_t* cfg_id, const uint8_t* first, uint8_t* decision, int64_t* remaining,
                                int64_t* retry_after_ns, int64_t* reset_at_ns, uint8_t* verdict);
+/* rl_charge_batch's signature without the store clock and the tokens: one Charge call (ask, decide, result) */
+typedef int (*rl_charge_fn)(void* user, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                            const uint32_t* cfg_id, uint8_t* decision, int64_t* charged, int64_t* remaining,
+                            int64_t* reset_at_ns);
 /* table counts / GC for the host backend (rl_table_info_get / rl_table_gc) */
 typedef int (*rl_info_fn)(void* user, int64_t now_ms, rl_table_info* out);
 typedef int (*rl_gc_fn)(void* user, int64_t now_ms, uint64_t tb_capacity, uint64_t win_capacity,
@@ -172,6 +187,15 @@ typedef struct rl_coalescer_backend {
     rl_allow_all_fn allow_all; /* nullable (and absent from a shorter struct): rl_coalescer_allow_all is then
                                   RL_EINVAL */
 } rl_coalescer_backend;
+
+/* rl_coalescer_backend with Charge's trailing function: pass &x.b with
+ * x.b.struct_size = sizeof x.  rl_coalescer_backend above is the struct up to
+ * allow_all, as a caller compiled before Charge passes it. */
+typedef struct rl_coalescer_backend_charge {
+    rl_coalescer_backend b;
+    rl_charge_fn charge;     /* nullable (and absent from a shorter struct): rl_coalescer_charge is then
+                                RL_EINVAL */
+} rl_coalescer_backend_charge;
 
 /* Coalescer over a GPU engine, on the device current on the calling thread
  * (the engine's: rl_engine_create makes it current).  The engine should be created with
@@ -275,6 +299,24 @@ int rl_coalescer_refund(rl_coalescer* c, size_t m, const uint64_t* key_id, const
 int rl_coalescer_allow_all(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
                            const uint32_t* cfg_id, const uint8_t* first, int64_t deadline_ns, uint8_t* decision,
                            int64_t* remaining, int64_t* retry_after_ns, int64_t* reset_at_ns, uint8_t* verdict);
+/* One Charge call (rl_charge_batch_device, include/rl_engine.h; the store clock
+ * of a request is floor(ts_ns / 1e6)): usage recorded after the fact, as one
+ * submission in sequence order.  Blocks until applied.  Every request gets its
+ * decision, charged, remaining and reset_at_ns as the engine call gives them.
+ * A submission is one launch and one engine call: never split (above
+ * max_batch, or above the engine's rl_charge_max: RL_EINVAL) and never merged
+ * with another -- merging makes duplicates, whose asks all read the state before
+ * the launch, so the results would depend on the timing of the queue.  A full
+ * queue refuses it (RL_EAGAIN).  Its requests insert keys: they count in the
+ * automatic GC's insert budgets and in stats.submitted / .decided; its launch
+ * counts in rl_coalescer_stats_charge.charge_launches.  deadline_ns (0 = none)
+ * and cancellation behave as for a decide submission.  With the usage tally or
+ * the top keys on, the requests are counted behind the launch as a decide
+ * batch's are, with the asked n and the verb's own decision.  RL_EINVAL over a
+ * host backend without `charge`. */
+int rl_coalescer_charge(rl_coalescer* c, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                        const uint32_t* cfg_id, int64_t deadline_ns, uint8_t* decision, int64_t* charged,
+                        int64_t* remaining, int64_t* reset_at_ns);
 /* Read-only queries (rl_peek_batch_device, include/rl_engine.h): for each
  * request the Result AllowN would return, against the state left by every
  * request submitted before the call and none submitted after it; nothing is
@@ -301,6 +343,9 @@ int rl_coalescer_snapshot(rl_coalescer* c, int64_t now_ms, uint32_t world, uint3
 int rl_coalescer_restore(rl_coalescer* c, const void* buf, size_t len, int64_t now_ms,
                          uint64_t tb_capacity, uint64_t win_capacity, rl_table_info* out);
 int rl_coalescer_get_stats(rl_coalescer* c, rl_coalescer_stats* out);
+/* the same counters and, behind them, charge_launches; struct_size comes back
+ * as the bytes filled in */
+int rl_coalescer_get_stats_charge(rl_coalescer* c, rl_coalescer_stats_charge* out);
 /* The usage tally (rl_tally_read's arguments, rl_engine.h) in sequence order
  * like rl_coalescer_table_info: it has counted every request submitted before
  * the call and none submitted after; nothing is drained.  With

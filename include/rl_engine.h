@@ -303,6 +303,75 @@ uint32_t rl_allow_all_max(rl_engine* e);
  * block size); a larger call strides */
 int rl_allow_all_grid_cap(void);
 
+/* Charge: record usage that is only known after the fact.  A call carries m
+ * requests (key_id, ts_ns, n, cfg_id, server_ms) as a decide batch does and has
+ * exactly the effect of three steps, placed between the batches enqueued before
+ * and after it:
+ *   1. ask      read-only.  A request with n <= 0, an unknown cfg_id or
+ *               RL_KEY_RESERVED is RL_INVALID and its n' is 0.  A token-bucket
+ *               request gets n' = min(n, r), r the `remaining` rl_peek_batch
+ *               returns for (key_id, n = 0) at the request's own ts_ns /
+ *               server_ms in the state left by every batch enqueued before the
+ *               call.  A window request (fixed or sliding) gets n' = n
+ *   2. decide   rl_decide_batch_device on (key_id, ts_ns, n', cfg_id,
+ *               server_ms) as one batch in array order; the requests with
+ *               n' = 0 are that batch's RL_INVALID requests and are not
+ *               executed.  Inserts, refill, expiry, spill and %.14g are that
+ *               call's
+ *   3. result   one row per request:
+ *               bucket, n' >= 1   charged = n' if the decide allowed it, else 0;
+ *                                 decision = RL_ALLOWED if charged == n,
+ *                                 RL_DENIED if charged < n, or the decide's
+ *                                 RL_ERROR / RL_INVALID; remaining, reset_at_ns
+ *                                 and tokens are the decide's
+ *               bucket, n' = 0    (an empty bucket) nothing ran and nothing is
+ *                                 stored: RL_DENIED, charged = 0, remaining = 0;
+ *                                 reset_at_ns and tokens are those of the ask
+ *               window            decision, remaining, reset_at_ns are the
+ *                                 decide's, tokens = 0; charged = n for
+ *                                 RL_ALLOWED or RL_DENIED, else 0.  RL_DENIED
+ *                                 means the whole n was recorded and the count is
+ *                                 now above the limit: the scripts INCRBY before
+ *                                 they compare (fixedwindow.go:22,
+ *                                 slidingwindow.go:24)
+ *               invalid           RL_INVALID, zeros
+ * There is no retry-after: nothing is being retried.  n - charged is what the
+ * bucket could not cover.
+ * For buckets that appear once in a call the verb is exact: Peek's parity with
+ * AllowN guarantees that the decide allows n'.  The verb is conservative about
+ * duplicates: the second request for a bucket has asked min(n, r) with r read
+ * before the first request's take, so the decide can deny it; its row then says
+ * RL_DENIED, charged = 0 and `remaining` as the decide read it, and the caller
+ * charges again.  In a call with one time stamp a bucket that refused any ask
+ * therefore ends with fewer whole tokens than that ask.  The exact sequential
+ * form is not offered.
+ * m <= rl_charge_max(e) = min(max_batch, 1 << 20), else RL_EINVAL: a call is
+ * never split.  m == 0 is RL_OK without a launch; null arrays with m > 0 are
+ * RL_EINVAL, except server_ms and tokens, which are nullable.  rl_stats moves as
+ * for the decide, and so does the sticky status; a full table rejects whole keys
+ * as the decide does, and those rows carry the decide's code and charged = 0.
+ * The first call allocates the engine's scratch, before anything is enqueued.
+ * Host arrays; synchronous; returns the sticky device status as rl_decide_batch
+ * does. */
+int rl_charge_batch(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                    const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* decision, int64_t* charged,
+                    int64_t* remaining, int64_t* reset_at_ns, double* tokens);
+/* Same, with device pointers: the ask is one kernel on the engine's replay
+ * stream, ordered as rl_peek_batch_device, and `stream` waits for it; the
+ * decide follows as rl_decide_batch_device enqueues it, except that n' is made
+ * on the device, so its grouping always waits for `stream`, whatever
+ * RL_OPT_PIPELINE says; the finish kernel runs on `stream` behind the decide.
+ * Calls may come from different streams: each call's ask waits for the previous
+ * call's finish before it writes the scratch again. */
+int rl_charge_batch_device(rl_engine* e, size_t m, const uint64_t* key_id, const int64_t* ts_ns, const int64_t* n,
+                           const uint32_t* cfg_id, const int64_t* server_ms, uint8_t* decision, int64_t* charged,
+                           int64_t* remaining, int64_t* reset_at_ns, double* tokens, void* stream);
+/* the largest Charge call */
+uint32_t rl_charge_max(rl_engine* e);
+/* requests one launch of the ask or the finish covers with one request per
+ * thread (grid cap x block size); a larger call strides */
+int rl_charge_grid_cap(void);
+
 /* Peek: read-only quota queries.  For each request, the outputs
  * rl_decide_batch would give for it at (ts_ns, server_ms) against the state
  * left by every batch enqueued before the call -- and nothing changes: no key

@@ -28,6 +28,7 @@ extern "C" {
 #define RLL_ERR_RESET    4  /* fmt.Errorf("failed to reset rate limit: %w") */
 #define RLL_ERR_ARG      5  /* bad C argument */
 #define RLL_ERR_REFUND   6  /* fmt.Errorf("failed to refund rate limit: %w"), in Reset's style */
+#define RLL_ERR_CHARGE   7  /* fmt.Errorf("failed to charge rate limit: %w") */
 
 #define RLL_NOW_WALL   INT64_MIN  /* now_ns: read the wall clock (time.Now()) */
 #define RLL_SMS_DEFAULT INT64_MIN /* server_ms: Redis clock = floor(now_ns / 1e6) */
@@ -146,6 +147,40 @@ int rll_refund_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int6
  * Any n <= 0 fails the whole call with RLL_ERR_INVALID_N, nothing applied. */
 int rll_refund_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens, const int64_t* n,
                     const int64_t* at_ns, int64_t now_ns, uint8_t* applied, char* err, size_t errlen);
+/* Charge: record usage that is only known after the fact (rl_charge_batch,
+ * include/rl_engine.h).  A token bucket gives up min(n, what it holds) and
+ * never goes below zero; a window counter records the whole n, over its limit
+ * or not (its script runs INCRBY before it compares).  *out: charged, short_by
+ * = n - charged, remaining, reset_at_unix_ns, and over_limit -- less than n was
+ * charged, or the window's count is now above its limit.  now_ns is the time of
+ * the request (RLL_NOW_WALL: the wall clock).  n <= 0 is RLL_ERR_INVALID_N
+ * before any I/O.  The key is interned as rll_allow_n interns it.  On a storage
+ * error (a closed limiter, a cancelled context, an engine failure, a request
+ * the engine could not execute) a fail-open limiter answers RLL_OK with
+ * charged = 0 and over_limit = 0 -- the usage is not recorded and nobody is
+ * held up --, a fail-closed one RLL_ERR_CHARGE with the message.  The metrics
+ * decorator counts rate_limiter_charged_units_total{algorithm} and
+ * rate_limiter_charge_short_units_total{algorithm}, exposed once the verb was
+ * used; the logging decorator logs a short charge at debug and a failed call
+ * at error level. */
+typedef struct rll_charge {
+    int64_t charged;
+    int64_t short_by;
+    int64_t remaining;
+    int64_t reset_at_unix_ns;
+    uint8_t over_limit;
+    uint8_t pad_[7];
+} rll_charge;
+int rll_charge_n(rll_limiter* l, const char* key, size_t keylen, int64_t n, int64_t now_ns, int ctx_cancelled,
+                 rll_charge* out, char* err, size_t errlen);
+/* m charges in ONE engine call, all at now_ns.  Within the call a later request
+ * for the same bucket asks against the state before the call: it can charge 0
+ * (over_limit = 1) where a call of its own would charge what is left, and the
+ * caller charges again.  Any n <= 0 fails the whole call with
+ * RLL_ERR_INVALID_N, nothing applied.  A fail-closed limiter fails the whole
+ * call on the first request the engine could not execute. */
+int rll_charge_many(rll_limiter* l, size_t m, const char* const* keys, const size_t* keylens, const int64_t* n,
+                    int64_t now_ns, int ctx_cancelled, rll_charge* out /* m */, char* err, size_t errlen);
 /* AllowAll: check one request against k limiters, 1 <= k <= 16, all on one
  * rll_engine (else RLL_ERR_ARG), all or nothing (rl_allow_all_batch,
  * include/rl_engine.h): one group of one engine call.  Quota stays taken only
