@@ -1226,6 +1226,14 @@ int rl::decide_after_stream(rl_engine* e, uint32_t m, const ReqArgs& a, hipStrea
     return run_batch(e, m, a, s, false);
 }
 
+int rl::decide_routed_after_stream(rl_engine* e, uint32_t m, const rl_route_rec* rec, const uint32_t* order,
+                                   const uint32_t* count, const int64_t* sms, rl_route_res* res, hipStream_t s,
+                                   hipEvent_t done) {
+    ReqArgs a{nullptr, nullptr, nullptr, nullptr, sms, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const RouteIn ri{rec, order, count, res};
+    return run_batch(e, m, a, s, false, nullptr, &ri, nullptr, done);
+}
+
 extern "C" int rl_decide_routed_device_io(rl_engine* e, size_t m_max, const uint32_t* count,
                                           const rl_route_rec* recv, const uint32_t* order, const int64_t* server_ms,
                                           rl_route_res* res, void* in_stream, void* out_stream) {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/rl_engine.h"
+#include "../../include/rl_route.h"
 #include "rl_batch.h"
 #include "rl_hot.h"
 #include "rl_semantics.h"
@@ -227,6 +228,14 @@ struct rl_engine {
         }
     } charge;
 
+    // The routed charge's scratch (rl_charge.h ChargeRouted): one allocation
+    // made by the first rl_charge_routed_device call, sized for rl_charge_max
+    // -- the normalised merged batch, the decide's result records and the
+    // ask's rows, by merge position.  `ev` is the end of the last call's finish
+    // kernel on `tail`: the next call's ask, on `chain`, waits for it before it
+    // writes the scratch again.
+    ChargeState charge_routed;
+
     // The tally's and the top keys' kernels run on the caller's stream and read
     // the feature's own memory: the end of the last such call on each stream
     // one was enqueued on is what drain(), rl_tally_read and rl_hot_read wait
@@ -305,6 +314,16 @@ int drain(rl_engine* e);
 // RL_OPT_PIPELINE says of the caller's arrays (Charge's second step,
 // rl_ops.hip).  Otherwise rl_decide_batch_device on one chunk.
 int decide_after_stream(rl_engine* e, uint32_t m, const ReqArgs& a, hipStream_t s);
+
+// One routed decide batch of bound m <= max_batch (include/rl_route.h: request
+// p is rec[order[p]] at store clock sms[p], p < *count; results to
+// res[order[p]]) whose inputs are made by work queued on s: the grouping waits
+// for s.  The end of its finish, on `tail`, is recorded into `done`; no stream
+// is made to wait.  The routed Charge's second step (rl_ops.hip), with s =
+// `chain`, where its ask ran.  Otherwise rl_decide_routed_device_ev.
+int decide_routed_after_stream(rl_engine* e, uint32_t m, const rl_route_rec* rec, const uint32_t* order,
+                               const uint32_t* count, const int64_t* sms, rl_route_res* res, hipStream_t s,
+                               hipEvent_t done);
 
 // slot ids (the sort keys) are 31 bits: token-bucket slots, then window slots,
 // then invalid_key

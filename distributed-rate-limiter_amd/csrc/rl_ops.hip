@@ -6,7 +6,8 @@
 // and a refund; the routed AllowAll's settle (rl_allow_all_settle_device) is
 // the second instantiation of that kernel's text.  Charge (rl_charge.h)
 // composes its ask as a chain op, a decide and its finish kernel on the
-// caller's stream.
+// caller's stream; the routed Charge the same three on the merged batch, its
+// decide on the engine's scratch and its finish on `tail`.
 // A code object of its own: that of the decision kernels (rl_engine.hip) does
 // not change with it.
 #include <hip/hip_runtime.h>
@@ -78,10 +79,13 @@ static int run_routed_op(rl_engine* e, bool reset, size_t m_max, const RoutedIo&
 static int run_refund_routed(rl_engine* e, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
                              hipEvent_t done);
 
+static int run_charge_routed(rl_engine* e, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
+                             hipEvent_t done);
+
 static int allow_all_warm_up(rl_engine* e);
 static int charge_warm_up(rl_engine* e);
 
-enum RoutedKind { ROUTED_PEEK, ROUTED_RESET, ROUTED_REFUND };
+enum RoutedKind { ROUTED_PEEK, ROUTED_RESET, ROUTED_REFUND, ROUTED_CHARGE };
 
 // the C-ABI of the routed steps: argument checks as rl_decide_routed_device_io
 // / _ev, except that m_max is bounded by the 32-bit `order` only
@@ -99,6 +103,7 @@ static int routed_op_entry(rl_engine* e, RoutedKind kind, size_t m_max, const ui
     const RoutedIo io{recv, order, count, server_ms, res, e->d_eflags};
     hipStream_t so = out_stream ? (hipStream_t)out_stream : s;
     if (kind == ROUTED_REFUND) return run_refund_routed(e, m_max, io, s, so, (hipEvent_t)done_event);
+    if (kind == ROUTED_CHARGE) return run_charge_routed(e, m_max, io, s, so, (hipEvent_t)done_event);
     return run_routed_op(e, kind == ROUTED_RESET, m_max, io, s, so, (hipEvent_t)done_event);
 }
 
@@ -123,13 +128,20 @@ extern "C" int rl_refund_routed_device(rl_engine* e, size_t m_max, const uint32_
                            done_event);
 }
 
+extern "C" int rl_charge_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                                       const uint32_t* order, const int64_t* server_ms, rl_route_res* res,
+                                       void* in_stream, void* out_stream, void* done_event) {
+    return routed_op_entry(e, ROUTED_CHARGE, m_max, count, recv, order, server_ms, res, in_stream, out_stream,
+                           done_event);
+}
+
 // The routed peek and reset steps on an empty batch (they read the zero count
 // and nothing else), then k_peek and k_reset_batch on one request that is
 // rejected: no config is registered yet.  The staging arrays hold zeros.
 // No refund kernel is launched here, routed or not: the first refund of an
 // engine allocates its scratch, and the warm-up allocates nothing.  Last,
 // AllowAll's settle kernel on one member, and Charge's two kernels on one
-// request.
+// request and its two routed kernels on an empty batch.
 int rl::ops_warm_up(rl_engine* e) {
     hipStream_t s = e->stream;
     const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
@@ -529,6 +541,22 @@ static int launch_charge_finish(rl_engine* e, size_t m, const int64_t* n, const 
     return RL_OK;
 }
 
+// the routed forms: the ask's grid is sized for the bound B, the finish's for
+// m_max (it also writes the dropped records past B); both stride
+static void launch_charge_ask_routed(rl_engine* e, size_t B, const RoutedIo& io, const ChargeRouted& R,
+                                     hipStream_t c) {
+    k_charge_ask_routed<<<grid_for(B, CHARGE_BLOCK, CHARGE_GRID), CHARGE_BLOCK, 0, c>>>(
+        (uint64_t)B, io, e->d_cfg, (uint32_t)e->h_cfg.size(), e->d_tb, e->tb_cap - 1, e->profile, R);
+}
+
+static int launch_charge_finish_routed(rl_engine* e, size_t B, size_t m_max, const RoutedIo& io,
+                                       const ChargeRouted& R, hipStream_t s) {
+    k_charge_finish_routed<<<grid_for(m_max, CHARGE_BLOCK, CHARGE_GRID), CHARGE_BLOCK, 0, s>>>(
+        (uint64_t)B, (uint64_t)m_max, io, R);
+    HIPCHK(e, hipGetLastError());
+    return RL_OK;
+}
+
 // One Charge call of 0 < m <= rl_charge_max requests with device pointers: the
 // ask as a chain op ordered like run_peek (s then sees n'), the decide on n' as
 // one batch whose grouping always waits for s -- n' is made on the device,
@@ -566,7 +594,77 @@ static int charge_warm_up(rl_engine* e) {
     hipStream_t s = e->stream;
     launch_charge_ask(e, 1, e->d_key, e->d_ts, e->d_n, e->d_cfgid, nullptr, S, s);
     HIPCHK(e, hipGetLastError());
-    return launch_charge_finish(e, 1, e->d_n, S, e->d_dec, e->d_retry, e->d_rem, e->d_reset, e->d_tok, s);
+    const int r = launch_charge_finish(e, 1, e->d_n, S, e->d_dec, e->d_retry, e->d_rem, e->d_reset, e->d_tok, s);
+    if (r != RL_OK) return r;
+    // the routed kernels on an empty batch: they read the zero count and
+    // nothing else, so no scratch stands behind the null pointers
+    const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
+    launch_charge_ask_routed(e, 1, io, ChargeRouted{}, s);
+    HIPCHK(e, hipGetLastError());
+    return launch_charge_finish_routed(e, 1, 1, io, ChargeRouted{}, s);
+}
+
+// the engine's routed Charge scratch, allocated by the first call: arrays of
+// rl_charge_max elements by merge position, the widest alignment first
+static int charge_routed_scratch(rl_engine* e, ChargeRouted* out) {
+    auto& A = e->charge_routed;
+    const size_t M = charge_max(e);
+    if (!A.ev) HIPCHK(e, hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
+    const size_t each = sizeof(rl_route_rec) + sizeof(rl_route_res) + sizeof(RoutedHalf) + sizeof(int64_t) +
+                        sizeof(uint32_t) + sizeof(uint8_t);
+    if (!A.mem && hipMalloc(&A.mem, M * each) != hipSuccess) {
+        A.mem = nullptr;
+        return fail(e, RL_ENOMEM, "routed Charge scratch: out of device memory");
+    }
+    out->rec2 = (rl_route_rec*)A.mem;
+    out->res2 = (rl_route_res*)(out->rec2 + M);
+    out->row = (RoutedHalf*)(out->res2 + M);
+    out->sms2 = (int64_t*)(out->row + M);
+    out->order2 = (uint32_t*)(out->sms2 + M);
+    out->kind = (uint8_t*)(out->order2 + M);
+    return RL_OK;
+}
+
+// enqueue the charge step of the routed path (include/rl_route.h): the merged
+// batch as ONE Charge call of bound B = min(m_max, rl_charge_max).
+//   ask      k_charge_ask_routed as a chain op ordered like run_routed_op's
+//            peek.  It always waits for s: count, order and the store clocks
+//            are the merge's outputs there.  It writes the normalised batch
+//            (n = n', order2[p] = p, the resolved clocks) and its rows into
+//            the engine's scratch; recv is not written.
+//   decide   the unchanged routed decide on the scratch, bound B, the caller's
+//            own count word.  Its grouping waits for `chain`, where the ask
+//            ran, not for a caller's stream; its results are scratch too.
+//   finish   k_charge_finish_routed on `tail`, in stream order behind the
+//            decide's finish: the result records at the receive indices, and
+//            RL_DROPPED past B.
+// The end of the finish is recorded into `done` when given, else so waits for
+// it.  No stream is added, the host waits for nothing and reads nothing.  The
+// scratch is allocated before anything is enqueued; the next routed charge's
+// ask waits for this call's finish (charge_routed.ev) before it writes the
+// scratch again.  rl_stats moves as for a routed decide of bound B; the flags
+// the call can raise are the decide's own and EF_ROUTED_OVER (a count above B).
+static int run_charge_routed(rl_engine* e, size_t m_max, const RoutedIo& io, hipStream_t s, hipStream_t so,
+                             hipEvent_t done) {
+    ChargeRouted R;
+    int r = charge_routed_scratch(e, &R);
+    if (r != RL_OK) return r;
+    auto& A = e->charge_routed;
+    const size_t B = std::min<size_t>(m_max, charge_max(e));
+    if (A.calls) HIPCHK(e, hipStreamWaitEvent(e->chain, A.ev, 0));
+    A.calls++;
+    // ev_peek is recorded behind the ask like a peek's; nothing waits for it
+    r = chain_op(e, s, false, nullptr, nullptr, e->ev_peek,
+                 [&](hipStream_t c) { launch_charge_ask_routed(e, B, io, R, c); });
+    if (r != RL_OK) return r;
+    r = decide_routed_after_stream(e, (uint32_t)B, R.rec2, R.order2, io.count, R.sms2, R.res2, e->chain, A.ev);
+    if (r == RL_OK) r = launch_charge_finish_routed(e, B, m_max, io, R, e->tail);
+    // recorded also after a failure: whatever was enqueued on `tail` is before it
+    HIPCHK(e, hipEventRecord(A.ev, e->tail));
+    if (r != RL_OK) return r;
+    if (done) HIPCHK(e, hipEventRecord(done, e->tail));
+    else HIPCHK(e, hipStreamWaitEvent(so, A.ev, 0));
+    return RL_OK;
 }
 
 extern "C" uint32_t rl_charge_max(rl_engine* e) { return e ? charge_max(e) : 0; }

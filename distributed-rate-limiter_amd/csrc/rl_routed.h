@@ -1,6 +1,7 @@
 // rl_routed.h -- the routed record form of a batch (include/rl_route.h) as the
-// one-request-per-thread kernels read it: k_peek_routed (rl_peek.h) and
-// k_reset_routed (rl_reset.h).
+// one-request-per-thread kernels read it: k_peek_routed (rl_peek.h),
+// k_reset_routed (rl_reset.h), k_refund_add_routed (rl_refund.h) and
+// k_charge_ask_routed / k_charge_finish_routed (rl_charge.h).
 //
 // The merge (rl_route_merge) leaves request p at rec[order[p]] with store
 // clock sms[p], p < *count -- a size in device memory, so a kernel is launched

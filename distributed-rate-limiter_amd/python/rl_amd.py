@@ -359,6 +359,7 @@ _sig = {
     "rl_peek_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
     "rl_reset_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
     "rl_refund_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
+    "rl_charge_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)
@@ -566,6 +567,23 @@ class Engine:
         if not event_p:
             raise ValueError("refund_routed_ev needs an event")
         self._routed_op(lib.rl_refund_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, None,
+                        event_p)
+
+    def charge_routed(self, m_max, count_p, recv_p, order_p, sms_p, res_p, stream=None, out_stream=None):
+        """rl_charge_routed_device: the charge step of the routed path -- the
+        merged batch as ONE Charge call (charge()) in merge order; result
+        records {decision, remaining, charged, reset_at} (`charged` in the
+        retry_after field), and {RL_DROPPED, 0, 0, 0} for the requests past
+        min(m_max, charge_max())"""
+        self._routed_op(lib.rl_charge_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream,
+                        out_stream, None)
+
+    def charge_routed_ev(self, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, event_p):
+        """the same with the results' completion recorded into the hipEvent_t
+        at event_p"""
+        if not event_p:
+            raise ValueError("charge_routed_ev needs an event")
+        self._routed_op(lib.rl_charge_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, None,
                         event_p)
 
     def decide_device(self, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, rem_p, retry_p, reset_p, tok_p,

@@ -54,8 +54,8 @@ def owner_of(key: np.ndarray, world: int) -> np.ndarray:
 INFO = 4   # RL_ROUTE_INFO
 
 # the kind of a routed step (every rank runs a step with the same kind)
-OP_DECIDE, OP_PEEK, OP_RESET, OP_REFUND = 0, 1, 2, 3
-_OP_NAMES = {OP_DECIDE: "decide", OP_PEEK: "peek", OP_RESET: "reset", OP_REFUND: "refund"}
+OP_DECIDE, OP_PEEK, OP_RESET, OP_REFUND, OP_CHARGE = 0, 1, 2, 3, 4
+_OP_NAMES = {OP_DECIDE: "decide", OP_PEEK: "peek", OP_RESET: "reset", OP_REFUND: "refund", OP_CHARGE: "charge"}
 
 
 def _ctx(stream):
@@ -127,12 +127,16 @@ class RoutedPipeline:
     requests' keys (n may be None); step(..., op=OP_REFUND) gives quota back
     (rl_refund_routed_device: all ranks' refunds of one target in the step are
     summed on the owner and applied once; decision REFUND_DONE, REFUND_NOKEY or
-    INVALID).  Such a step is packed, exchanged, merged
+    INVALID); step(..., op=OP_CHARGE) records usage known after the fact
+    (rl_charge_routed_device: the merged batch is one Charge call in merge
+    order; dec / rem / reset as for a decide, and the `retry` output array
+    receives `charged`).  Such a step is packed, exchanged, merged
     and unpacked exactly as a decide step -- same buffer sets, collectives,
     collective order and lookahead -- and only the owner's engine call differs:
-    peek / reset / refund (the signature of decide: rl_peek_routed_device /
-    rl_reset_routed_device / rl_refund_routed_device with out_stream) or
-    peek_ev / reset_ev / refund_ev (that of decide_ev).  Every rank must give a
+    peek / reset / refund / charge (the signature of decide:
+    rl_peek_routed_device / rl_reset_routed_device / rl_refund_routed_device /
+    rl_charge_routed_device with out_stream) or peek_ev / reset_ev / refund_ev /
+    charge_ev (that of decide_ev).  Every rank must give a
     step the same kind.  The engine orders
     the step after every step issued before it and before every later one.
 
@@ -143,7 +147,7 @@ class RoutedPipeline:
 
     def __init__(self, ops, decide, world, max_batch, device, pg_req=None, pg_res=None, depth=4, exchange=None,
                  staged=False, lookahead=None, ordered=True, decide_ev=None, *, peek=None, peek_ev=None, reset=None,
-                 reset_ev=None, refund=None, refund_ev=None, settle=None):
+                 reset_ev=None, refund=None, refund_ev=None, settle=None, charge=None, charge_ev=None):
         self.ops, self.decide, self.world = ops, decide, world
         # settle(m, first, cfg, n, dec, verdict, g, sel, stream): the sender's
         # settle of allow_all (rl_allow_all_settle_device; device pointers)
@@ -182,13 +186,14 @@ class RoutedPipeline:
         # between, and serialize the engine's steps
         self.decide_ev = decide_ev if self.cuda else None
         # per step kind: (call with out_stream, call with event); a peek,
-        # reset or refund step takes the event form when it is given, like the
+        # reset, refund or charge step takes the event form when it is given, like the
         # decide
         self._calls = {
             OP_DECIDE: (decide, self.decide_ev),
             OP_PEEK: (peek, peek_ev if self.cuda else None),
             OP_RESET: (reset, reset_ev if self.cuda else None),
             OP_REFUND: (refund, refund_ev if self.cuda else None),
+            OP_CHARGE: (charge, charge_ev if self.cuda else None),
         }
         with_events = any(ev is not None for _, ev in self._calls.values())
         self._zero_n = None           # n of a reset step given without one
@@ -268,7 +273,8 @@ class RoutedPipeline:
         [(b', stream)] whose result sides this call issued: b' is complete on
         `stream`.  op: the step's kind, the same on every rank (OP_PEEK: the
         answers with nothing changed; OP_RESET: the keys deleted, n ignored
-        and may be None; OP_REFUND: n units given back per request)."""
+        and may be None; OP_REFUND: n units given back per request; OP_CHARGE:
+        n units of usage recorded per request, `retry` receives `charged`)."""
         if op not in self._calls:
             raise ValueError(f"RoutedPipeline: unknown step kind {op!r}")
         call, call_ev = self._calls[op]

@@ -39,8 +39,9 @@
  *            rl_decide_routed_device: the owner's engine reads the received
  *                               records in that order and writes 32-byte
  *                               result records at their receive index
- *            (a peek, reset or refund step calls rl_peek_routed_device /
- *                               rl_reset_routed_device / rl_refund_routed_device
+ *            (a peek, reset, refund or charge step calls
+ *                               rl_peek_routed_device / rl_reset_routed_device /
+ *                               rl_refund_routed_device / rl_charge_routed_device
  *                               here instead; see there)
  *            equal-split all-to-all of the result buckets back
  *   sender   rl_route_unpack    results to the caller's order
@@ -269,6 +270,63 @@ int rl_reset_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, co
  * refund of an engine, routed or not, allocates the scratch (m_max == 0
  * allocates nothing and records done_event on in_stream). */
 int rl_refund_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                            const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
+                            void* out_stream, void* done_event);
+
+/* Charge step: the routed form of rl_charge_batch (include/rl_engine.h,
+ * DESIGN.md §10m, §10n) -- usage that is only known after the fact, recorded
+ * on the key's owner GPU in order with the routed steps in flight.  A charge
+ * step is homogeneous like the other kinds and is packed, exchanged, merged
+ * and unpacked exactly as a decide step -- the router does not change and the
+ * wire record carries no op code; the owner calls this instead of
+ * rl_decide_routed_device.  Arguments, argument checks and the stream / event
+ * behaviour are those of rl_refund_routed_device.
+ *   request p   recv[order[p]] at store clock server_ms[p] (or the
+ *          RL_ORDER_IDENTITY form): a charge (key, ts, n, cfg, store clock) with
+ *          the meaning of rl_charge_batch.
+ *   one call    the merged batch is ONE Charge call in merge order -- the three
+ *          steps of rl_charge_batch with "array order" read as merge position p.
+ *          Ask: every request is asked against the state left by every engine
+ *          call issued before this step: n' = min(n, Peek(key, 0).remaining) for
+ *          a token bucket, n' = n for a window, 0 for an invalid request.
+ *          Decide: the unchanged routed decide runs on n' as one batch.  Result:
+ *          the rule of rl_charge_batch.
+ *          All ranks' charges of one bucket in a step are therefore duplicates
+ *          of one call.  The verb is exact for a bucket that appears once in the
+ *          merged batch and conservative otherwise: every duplicate was asked
+ *          against the same state, so a later one can find less than its n',
+ *          takes nothing and is RL_DENIED with charged 0 -- the caller charges
+ *          again.  The bound of rl_charge_batch holds across ranks: at one time
+ *          stamp, a bucket that refused any ask ends with fewer whole tokens
+ *          than that ask, and never below zero.  Windows INCRBY before they
+ *          compare, so every window charge is recorded in full.
+ *   result      one rl_route_res at res[order[p]]: {decision, remaining,
+ *          charged, reset_at_ns}.  `charged` travels in the record's retry_after
+ *          field -- nothing is retried after a charge -- so rl_route_unpack
+ *          delivers it into the caller's retry_after_ns array.  decision:
+ *          RL_ALLOWED when charged == n; RL_DENIED when less was taken (a bucket)
+ *          or the window is now over its limit (charged == n all the same);
+ *          RL_ERROR / RL_INVALID as the decide's.  An empty bucket's row is
+ *          {RL_DENIED, 0, 0, the ask's reset_at}.  `tokens` is not carried, as
+ *          in every routed result.
+ *   bound       the call executes the first B = min(m_max, rl_charge_max(e))
+ *          requests of the merged batch, as one call (the scratch is sized for
+ *          rl_charge_max).  m_max itself is limited only by the 32-bit `order`.
+ *          If *count > B, the requests B <= p < min(*count, m_max) get
+ *          {RL_DROPPED, 0, 0, 0} -- not executed, to be resubmitted -- and the
+ *          next rl_engine_sync returns RL_EOVERFLOW, the only sticky status the
+ *          call adds to the decide's own (a full table: RL_ENOMEM).
+ *   counters    rl_stats moves as a routed decide of bound B moves it; the
+ *          tally, the top keys and the GC budgets do not move.
+ * Order: the ask is a chain op like a peek step's kernel, after every engine
+ * call issued before the step; the decide is ordered as any routed decide; the
+ * finish runs on the engine's finish stream behind the decide's.  `recv`,
+ * `order`, `server_ms` and `count` are only read.  Store clock: a charge step
+ * advances the router's store clock like any step; a request dropped at its
+ * sender comes back RL_DROPPED and was not recorded.  The first routed charge
+ * of an engine allocates its scratch before anything is enqueued (m_max == 0
+ * allocates nothing and records done_event on in_stream). */
+int rl_charge_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
                             const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
                             void* out_stream, void* done_event);
 
