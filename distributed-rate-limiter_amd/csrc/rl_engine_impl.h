@@ -180,6 +180,7 @@ struct rl_engine {
     uint32_t tally_cfg_cap = 0;
     rl::tally_u64* d_tally_glob = nullptr;    // TG_WORDS
     uint64_t tally_batches = 0, tally_requests = 0;
+    uint64_t tally_routed_steps = 0;          // rl_tally_routed_device calls with m_max > 0
 
     // top keys (rl_hot.h): off until rl_hot_enable
     bool hot_on = false;

@@ -37,6 +37,12 @@
 // or m.  The kernels hold pointers to the four input arrays and the feature's
 // own three allocations only.
 //
+// k_hot_add_routed / k_hot_pick_routed count a finished routed step on the
+// key's owner GPU (include/rl_route.h rl_hot_routed_device):
+// the same texts, hot_add_requests<Read> / hot_pick_requests<Read>, with
+// hot_request reading request p from its 32-byte record and the decision from
+// the 32-byte result record at the same receive index.
+//
 // The kernels are compiled in a translation unit of their own (rl_hot.hip,
 // which defines RL_HOT_DEVICE, with the rl_hot_* entry points): the other units
 // include this header through rl_engine_impl.h for the types only and gain no
@@ -46,6 +52,9 @@
 #include <hip/hip_runtime.h>
 
 #include "rl_table.h"
+#ifdef RL_HOT_DEVICE
+#include "rl_routed.h"
+#endif
 
 namespace rl {
 
@@ -106,23 +115,38 @@ __device__ __forceinline__ hot_u64 hot_estimate(const hot_u64* sketch, uint64_t 
     return est;
 }
 
-// request i of the batch: key, config and weight; whether it counts.  i >= m
-// is neither counted nor skipped (*valid false).
-__device__ __forceinline__ bool hot_request(uint64_t i, uint64_t m, const uint64_t* __restrict__ key,
-                                            const uint32_t* __restrict__ cfg, const int64_t* __restrict__ n,
-                                            const uint8_t* __restrict__ dec, uint32_t ncfg, uint32_t units,
+// request i of a finished batch in the decide layout: the array form's reader
+// (n is read in units mode only)
+struct HotArrays {
+    const uint64_t* __restrict__ key;
+    const uint32_t* __restrict__ cfg;
+    const int64_t* __restrict__ n;
+    const uint8_t* __restrict__ dec;
+    __device__ __forceinline__ void operator()(uint64_t i, bool want_n, uint64_t& k, uint32_t& c, int64_t& nn,
+                                               uint32_t& d) const {
+        k = key[i];
+        c = cfg[i];
+        d = dec[i];
+        nn = want_n ? n[i] : 0;
+    }
+};
+
+// request i of the batch as `rd` reads it (HotArrays, or RoutedCount of
+// rl_routed.h for a routed step): key, config and weight; whether it counts.
+// i >= m is neither counted nor skipped (*valid false).
+template <class Read>
+__device__ __forceinline__ bool hot_request(uint64_t i, uint64_t m, const Read& rd, uint32_t ncfg, uint32_t units,
                                             uint64_t* k, uint32_t* c, hot_u64* w, bool* valid) {
     *valid = i < m;
     *k = EMPTY_KEY;
     *c = 0xffffffffu;
     *w = 0;
     if (!*valid) return false;
-    *k = key[i];
-    *c = cfg[i];
-    const uint32_t d = dec[i];
+    int64_t nn;
+    uint32_t d;
+    rd(i, units != 0, *k, *c, nn, d);
     bool counted = *c < ncfg && d <= 2u && *k != EMPTY_KEY;
     if (units) {
-        const int64_t nn = n[i];
         counted = counted && nn > 0;
         *w = counted ? (hot_u64)nn : 0;
     } else {
@@ -131,12 +155,12 @@ __device__ __forceinline__ bool hot_request(uint64_t i, uint64_t m, const uint64
     return counted;
 }
 
-__global__ __launch_bounds__(HOT_BLOCK) void k_hot_add(uint64_t m, const uint64_t* __restrict__ key,
-                                                       const uint32_t* __restrict__ cfg,
-                                                       const int64_t* __restrict__ n,
-                                                       const uint8_t* __restrict__ dec, uint32_t ncfg, uint32_t units,
-                                                       hot_u64* __restrict__ sketch, uint64_t width,
-                                                       hot_u64* __restrict__ glob) {
+// The adds of requests 0 .. m - 1 as `rd` reads them: the text of k_hot_add and
+// k_hot_add_routed.  m must be uniform over the block.
+template <class Read>
+__device__ __forceinline__ void hot_add_requests(uint64_t m, const Read& rd, uint32_t ncfg, uint32_t units,
+                                                 hot_u64* __restrict__ sketch, uint64_t width,
+                                                 hot_u64* __restrict__ glob) {
     __shared__ hot_u64 s_key[HOT_LDS_KEYS], s_w[HOT_LDS_KEYS];
     __shared__ hot_u64 s_glob[2];                        // HG_TOTAL, HG_SKIPPED
     const uint32_t tid = threadIdx.x;
@@ -151,7 +175,7 @@ __global__ __launch_bounds__(HOT_BLOCK) void k_hot_add(uint64_t m, const uint64_
         uint32_t c;
         hot_u64 w;
         bool valid;
-        const bool counted = hot_request(base + tid, m, key, cfg, n, dec, ncfg, units, &k, &c, &w, &valid);
+        const bool counted = hot_request(base + tid, m, rd, ncfg, units, &k, &c, &w, &valid);
         hot_u64 pend = __ballot(counted);
         const hot_u64 skip = __ballot(valid && !counted);
         // the wave's total and skipped, once per wave
@@ -199,6 +223,29 @@ __global__ __launch_bounds__(HOT_BLOCK) void k_hot_add(uint64_t m, const uint64_
     if (tid < 2 && s_glob[tid]) hot_add(&glob[tid == 0 ? HG_TOTAL : HG_SKIPPED], s_glob[tid]);
 }
 
+__global__ __launch_bounds__(HOT_BLOCK) void k_hot_add(uint64_t m, const uint64_t* __restrict__ key,
+                                                       const uint32_t* __restrict__ cfg,
+                                                       const int64_t* __restrict__ n,
+                                                       const uint8_t* __restrict__ dec, uint32_t ncfg, uint32_t units,
+                                                       hot_u64* __restrict__ sketch, uint64_t width,
+                                                       hot_u64* __restrict__ glob) {
+    hot_add_requests(m, HotArrays{key, cfg, n, dec}, ncfg, units, sketch, width, glob);
+}
+
+// The adds of a finished routed step on its owner (rl_hot_routed_device):
+// request p < min(m_max, *count) of the merged batch, in either form of the
+// merge, with the decision of its result record.  The grid is sized for the
+// caller's bound, since the host does not know the count; every thread reads
+// *count, so the trip count is uniform over the block.  A count above m_max
+// re-raises EF_ROUTED_OVER (routed_open's atomicOr, the flag the decide raised
+// already); every other store goes to the feature's own memory.
+__global__ __launch_bounds__(HOT_BLOCK) void k_hot_add_routed(uint64_t m_max, RoutedIo io, uint32_t ncfg,
+                                                              uint32_t units, hot_u64* __restrict__ sketch,
+                                                              uint64_t width, hot_u64* __restrict__ glob) {
+    const RoutedForm f = routed_open(m_max, io);
+    hot_add_requests(f.m, RoutedCount{io, f}, ncfg, units, sketch, width, glob);
+}
+
 // key k (hash h = mix64(k)) qualifies: find its record or claim one; without a
 // slot, dropped
 __device__ inline void hot_claim(HotKey* keys, uint64_t mask, uint64_t probes, hot_u64* glob, uint64_t k, uint64_t h,
@@ -220,21 +267,21 @@ __device__ inline void hot_claim(HotKey* keys, uint64_t mask, uint64_t probes, h
     __hip_atomic_store(&glob[HG_DROPPED], (hot_u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(HOT_BLOCK) void k_hot_pick(uint64_t m, const uint64_t* __restrict__ key,
-                                                        const uint32_t* __restrict__ cfg,
-                                                        const int64_t* __restrict__ n,
-                                                        const uint8_t* __restrict__ dec, uint32_t ncfg, uint32_t units,
-                                                        const hot_u64* __restrict__ sketch, uint64_t width,
-                                                        hot_u64 hot_min, hot_u64* __restrict__ glob,
-                                                        HotKey* __restrict__ keys, uint64_t mask, uint64_t probes) {
+// The look at the keys of requests 0 .. m - 1 as `rd` reads them: the text of
+// k_hot_pick and k_hot_pick_routed.  m must be uniform over the block.
+template <class Read>
+__device__ __forceinline__ void hot_pick_requests(uint64_t m, const Read& rd, uint32_t ncfg, uint32_t units,
+                                                  const hot_u64* __restrict__ sketch, uint64_t width, hot_u64 hot_min,
+                                                  hot_u64* __restrict__ glob, HotKey* __restrict__ keys, uint64_t mask,
+                                                  uint64_t probes) {
     const uint32_t lane = threadIdx.x & 63u;
-    // block-uniform trip count, as in k_hot_add
+    // block-uniform trip count, as in hot_add_requests
     for (uint64_t base = blockIdx.x * (uint64_t)HOT_BLOCK; base < m; base += (uint64_t)gridDim.x * HOT_BLOCK) {
         uint64_t k;
         uint32_t c;
         hot_u64 w;
         bool valid;
-        const bool counted = hot_request(base + threadIdx.x, m, key, cfg, n, dec, ncfg, units, &k, &c, &w, &valid);
+        const bool counted = hot_request(base + threadIdx.x, m, rd, ncfg, units, &k, &c, &w, &valid);
         hot_u64 pend = __ballot(counted);
         bool lead_me = false;
         for (int it = 0; it < 64 && pend; it++) {        // wave-uniform: pend is a ballot
@@ -247,6 +294,26 @@ __global__ __launch_bounds__(HOT_BLOCK) void k_hot_pick(uint64_t m, const uint64
         }
         if (lead_me && hot_estimate(sketch, width, k) >= hot_min) hot_claim(keys, mask, probes, glob, k, mix64(k), c);
     }
+}
+
+__global__ __launch_bounds__(HOT_BLOCK) void k_hot_pick(uint64_t m, const uint64_t* __restrict__ key,
+                                                        const uint32_t* __restrict__ cfg,
+                                                        const int64_t* __restrict__ n,
+                                                        const uint8_t* __restrict__ dec, uint32_t ncfg, uint32_t units,
+                                                        const hot_u64* __restrict__ sketch, uint64_t width,
+                                                        hot_u64 hot_min, hot_u64* __restrict__ glob,
+                                                        HotKey* __restrict__ keys, uint64_t mask, uint64_t probes) {
+    hot_pick_requests(m, HotArrays{key, cfg, n, dec}, ncfg, units, sketch, width, hot_min, glob, keys, mask, probes);
+}
+
+// the same over the routed step k_hot_add_routed counted, behind it on the stream
+__global__ __launch_bounds__(HOT_BLOCK) void k_hot_pick_routed(uint64_t m_max, RoutedIo io, uint32_t ncfg,
+                                                               uint32_t units, const hot_u64* __restrict__ sketch,
+                                                               uint64_t width, hot_u64 hot_min,
+                                                               hot_u64* __restrict__ glob, HotKey* __restrict__ keys,
+                                                               uint64_t mask, uint64_t probes) {
+    const RoutedForm f = routed_open(m_max, io);
+    hot_pick_requests(f.m, RoutedCount{io, f}, ncfg, units, sketch, width, hot_min, glob, keys, mask, probes);
 }
 
 // every candidate's estimate from the sketch as it is now (rl_hot_read)

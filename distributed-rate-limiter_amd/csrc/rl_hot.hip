@@ -29,6 +29,20 @@ static hipError_t hot_pick_launch(rl_engine* e, uint64_t m, const uint64_t* key,
     return hipGetLastError();
 }
 
+// k_hot_add_routed, then k_hot_pick_routed, over the merged routed step `io` of bound m_max
+static hipError_t hot_routed_launch(rl_engine* e, uint64_t m_max, const RoutedIo& io, hipStream_t s) {
+    const uint32_t ncfg = (uint32_t)e->h_cfg.size();
+    k_hot_add_routed<<<hot_grid(m_max), HOT_BLOCK, 0, s>>>(m_max, io, ncfg, e->hot_weight, e->d_hot_sketch,
+                                                           e->hot_width, e->d_hot_glob);
+    hipError_t st = hipGetLastError();
+    if (st != hipSuccess) return st;
+    k_hot_pick_routed<<<hot_grid(m_max), HOT_BLOCK, 0, s>>>(m_max, io, ncfg, e->hot_weight, e->d_hot_sketch,
+                                                            e->hot_width, e->hot_min, e->d_hot_glob, e->d_hot_keys,
+                                                            e->hot_slots - 1,
+                                                            std::min<uint64_t>(e->hot_slots, HOT_PROBES));
+    return hipGetLastError();
+}
+
 static hipError_t hot_clear_launch(rl_engine* e, hipStream_t s) {
     k_hot_clear<<<256, 256, 0, s>>>(e->d_hot_sketch, (uint64_t)HOT_DEPTH * e->hot_width, e->d_hot_keys, e->hot_slots,
                                     e->d_hot_glob);
@@ -74,6 +88,9 @@ extern "C" int rl_hot_enable(rl_engine* e, const rl_hot_opts* o) {
         // empty launches load the kernels now, not in front of the first batch
         ok = ok && hot_add_launch(e, 0, nullptr, nullptr, nullptr, nullptr, e->stream) == hipSuccess;
         ok = ok && hot_pick_launch(e, 0, nullptr, nullptr, nullptr, nullptr, e->stream) == hipSuccess;
+        // the routed forms on a zero count
+        ok = ok && hot_routed_launch(e, 0, RoutedIo{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags},
+                                     e->stream) == hipSuccess;
         k_hot_read<<<1, 256, 0, e->stream>>>(e->d_hot_keys, 0, e->d_hot_sketch, e->hot_width);
         ok = ok && hipGetLastError() == hipSuccess;
         ok = ok && hipStreamSynchronize(e->stream) == hipSuccess;
@@ -178,6 +195,24 @@ extern "C" int rl_hot_read(rl_engine* e, rl_hot_key* key_out, size_t key_cap, ui
         e->hot_batches = e->hot_requests = 0;
     }
     return RL_OK;
+}
+
+// The routed form (include/rl_route.h): the adds, then the pick, on the
+// caller's stream behind the step's results; like the array form they touch
+// the feature's own memory only (and re-raise EF_ROUTED_OVER on a count above
+// m_max), so they use none of the engine's streams and are waited for through
+// side_record's events.  hot_batches / hot_requests count array calls only.
+extern "C" int rl_hot_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                                    const uint32_t* order, const int64_t* server_ms, const rl_route_res* res,
+                                    void* stream) {
+    if (!e || !e->hot_on || m_max > 0xffffffffull) return RL_EINVAL;
+    if (m_max == 0) return RL_OK;
+    if (!count || !recv || !order || !server_ms || !res) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    const RoutedIo io{recv, order, count, server_ms, const_cast<rl_route_res*>(res), e->d_eflags};   // res is only read
+    HIPCHK(e, hot_routed_launch(e, (uint64_t)m_max, io, s));
+    return side_record(e, s);
 }
 
 extern "C" int rl_hot_grid_cap(void) { return HOT_GRID * HOT_BLOCK; }

@@ -1,7 +1,9 @@
 // rl_routed.h -- the routed record form of a batch (include/rl_route.h) as the
 // one-request-per-thread kernels read it: k_peek_routed (rl_peek.h),
-// k_reset_routed (rl_reset.h), k_refund_add_routed (rl_refund.h) and
-// k_charge_ask_routed / k_charge_finish_routed (rl_charge.h).
+// k_reset_routed (rl_reset.h), k_refund_add_routed (rl_refund.h),
+// k_charge_ask_routed / k_charge_finish_routed (rl_charge.h), and the counting
+// kernels k_tally_routed (rl_tally.h) and k_hot_add_routed / k_hot_pick_routed
+// (rl_hot.h), which read a finished step through RoutedCount.
 //
 // The merge (rl_route_merge) leaves request p at rec[order[p]] with store
 // clock sms[p], p < *count -- a size in device memory, so a kernel is launched
@@ -77,6 +79,30 @@ __device__ inline rl_route_rec routed_request(const RoutedIo& io, const RoutedFo
     }
     return r;
 }
+
+// A finished routed step as the counting kernels read it (k_tally_routed,
+// rl_tally.h; k_hot_add_routed / k_hot_pick_routed, rl_hot.h): request p < f.m
+// is (key, cfg, n) of its record and the decision of the result record at the
+// same receive index -- the 16-byte half that holds it; the store clock and
+// pos are not used.  The decision is an int64 here: a value outside 0..3,
+// negative ones included, reads as the code 0xff, which no counting rule
+// accepts.  The reader's call is that of the array forms' readers (TallyArrays,
+// HotArrays), so the text after the read is one text.
+struct RoutedCount {
+    RoutedIo io;
+    RoutedForm f;
+    __device__ __forceinline__ void operator()(uint64_t p, bool, uint64_t& k, uint32_t& c, int64_t& n,
+                                               uint32_t& d) const {
+        uint32_t at;
+        int64_t sms;
+        const rl_route_rec r = routed_request(io, f, p, at, sms);
+        const int64_t dec = reinterpret_cast<const RoutedHalf*>(io.res + at)[0].a;
+        k = r.key;
+        c = r.cfg;
+        n = r.n;
+        d = (uint64_t)dec <= 3u ? (uint32_t)dec : 0xffu;
+    }
+};
 
 // the result record at receive index `at`, as two 16-byte stores
 __device__ inline void routed_result(const RoutedIo& io, uint32_t at, int64_t decision, int64_t remaining,

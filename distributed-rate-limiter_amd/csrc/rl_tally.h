@@ -37,6 +37,11 @@
 // every loop is bounded by 64, the probe bound, or m.  The kernel stores to
 // the tally's own memory only: it holds no pointer to a state table.
 //
+// k_tally_routed counts a finished routed step on the key's owner GPU
+// (include/rl_route.h rl_tally_routed_device): the same text,
+// tally_requests<Read>, reading request p from its 32-byte record and the
+// decision from the 32-byte result record at the same receive index.
+//
 // The kernels are compiled in a translation unit of their own (rl_tally.hip,
 // which defines RL_TALLY_DEVICE, with the rl_tally_* entry points): the other
 // units include this header through rl_engine_impl.h for the types only and
@@ -46,6 +51,9 @@
 #include <hip/hip_runtime.h>
 
 #include "rl_table.h"
+#ifdef RL_TALLY_DEVICE
+#include "rl_routed.h"
+#endif
 
 namespace rl {
 
@@ -60,6 +68,8 @@ constexpr int TALLY_CFG_WORDS = 6;         // count[4], units[2]
 
 // global words
 constexpr int TG_UNKNOWN = 0, TG_BAD = 1, TG_UNTRACKED_REQ = 2, TG_UNTRACKED_UNITS = 3, TG_KEYS = 4, TG_WORDS = 8;
+// ... of the routed form (k_tally_routed): requests looked at, requests dropped at their senders
+constexpr int TG_ROUTED_REQ = 5, TG_ROUTED_DROPPED = 6;
 
 struct TallyKey {      // rl_tally_key
     uint64_t key;      // EMPTY_KEY: free
@@ -115,12 +125,29 @@ __device__ inline void tally_upsert(TallyKey* keys, uint64_t mask, uint64_t prob
     if (units) tally_add(&glob[TG_UNTRACKED_UNITS], units);
 }
 
-__global__ __launch_bounds__(TALLY_BLOCK) void k_tally(uint64_t m, const uint64_t* __restrict__ key,
-                                                       const uint32_t* __restrict__ cfg,
-                                                       const int64_t* __restrict__ n,
-                                                       const uint8_t* __restrict__ dec, uint32_t ncfg,
-                                                       tally_u64* __restrict__ cfgc, tally_u64* __restrict__ glob,
-                                                       TallyKey* __restrict__ keys, uint64_t mask, uint64_t probes) {
+// request i of a finished batch in the decide layout: the array form's reader
+struct TallyArrays {
+    const uint64_t* __restrict__ key;
+    const uint32_t* __restrict__ cfg;
+    const int64_t* __restrict__ n;
+    const uint8_t* __restrict__ dec;
+    __device__ __forceinline__ void operator()(uint64_t i, bool, uint64_t& k, uint32_t& c, int64_t& nn,
+                                               uint32_t& d) const {
+        k = key[i];
+        c = cfg[i];
+        nn = n[i];
+        d = dec[i];
+    }
+};
+
+// The tally of requests 0 .. m - 1 as `rd` reads them: the text of k_tally
+// (Read = TallyArrays) and k_tally_routed (Read = RoutedCount, rl_routed.h).
+// Only the read differs; the counting rules, the three merges and every atomic
+// are this one text.  m must be uniform over the block.
+template <class Read>
+__device__ __forceinline__ void tally_requests(uint64_t m, const Read& rd, uint32_t ncfg,
+                                               tally_u64* __restrict__ cfgc, tally_u64* __restrict__ glob,
+                                               TallyKey* __restrict__ keys, uint64_t mask, uint64_t probes) {
     __shared__ tally_u64 s_cfg[TALLY_LDS_CFGS * TALLY_CFG_WORDS];
     __shared__ tally_u64 s_glob[2];                      // TG_UNKNOWN, TG_BAD
     __shared__ tally_u64 s_key[TALLY_LDS_KEYS], s_den[TALLY_LDS_KEYS], s_units[TALLY_LDS_KEYS];
@@ -140,10 +167,8 @@ __global__ __launch_bounds__(TALLY_BLOCK) void k_tally(uint64_t m, const uint64_
         uint32_t c = 0xffffffffu, d = 0xffu;
         tally_u64 u = 0;
         if (valid) {
-            k = key[i];
-            c = cfg[i];
-            const int64_t nn = n[i];
-            d = dec[i];
+            int64_t nn;
+            rd(i, true, k, c, nn, d);
             u = nn > 0 ? (tally_u64)nn : 0;
         }
         const bool counted = valid && c < ncfg && d <= 3u;
@@ -219,6 +244,44 @@ __global__ __launch_bounds__(TALLY_BLOCK) void k_tally(uint64_t m, const uint64_
     if (tid < 2 && s_glob[tid]) tally_add(&glob[tid == 0 ? TG_UNKNOWN : TG_BAD], s_glob[tid]);
     if (tid < TALLY_LDS_KEYS && s_key[tid] != EMPTY_KEY)
         tally_upsert(keys, mask, probes, glob, s_key[tid], mix64(s_key[tid]), s_kcfg[tid], s_den[tid], s_units[tid]);
+}
+
+__global__ __launch_bounds__(TALLY_BLOCK) void k_tally(uint64_t m, const uint64_t* __restrict__ key,
+                                                       const uint32_t* __restrict__ cfg,
+                                                       const int64_t* __restrict__ n,
+                                                       const uint8_t* __restrict__ dec, uint32_t ncfg,
+                                                       tally_u64* __restrict__ cfgc, tally_u64* __restrict__ glob,
+                                                       TallyKey* __restrict__ keys, uint64_t mask, uint64_t probes) {
+    tally_requests(m, TallyArrays{key, cfg, n, dec}, ncfg, cfgc, glob, keys, mask, probes);
+}
+
+// The tally of a finished routed step on its owner (rl_tally_routed_device):
+// request p < min(m_max, *count) of the merged batch, in either form of the
+// merge, with the decision of its result record.  The grid is sized for the
+// caller's bound, min(ceil(m_max / TALLY_BLOCK), TALLY_GRID) blocks, since the
+// host does not know the count; every thread reads *count, so the trip count
+// ceil(min(m_max, *count) / TALLY_BLOCK) rounds of the grid is uniform over the
+// block.  A count above m_max re-raises EF_ROUTED_OVER (routed_open's atomicOr,
+// the flag the decide raised already); every other store goes to the tally's
+// own memory.  One thread adds the step's size to TG_ROUTED_REQ and, with the
+// received info rows, the requests the `world` senders dropped for this owner
+// (row 3 >> 1 of each source: they never arrived, so nothing else shows them)
+// to TG_ROUTED_DROPPED.
+__global__ __launch_bounds__(TALLY_BLOCK) void k_tally_routed(uint64_t m_max, RoutedIo io,
+                                                              const int64_t* __restrict__ recv_info, uint32_t world,
+                                                              uint32_t ncfg, tally_u64* __restrict__ cfgc,
+                                                              tally_u64* __restrict__ glob,
+                                                              TallyKey* __restrict__ keys, uint64_t mask,
+                                                              uint64_t probes) {
+    const RoutedForm f = routed_open(m_max, io);
+    tally_requests(f.m, RoutedCount{io, f}, ncfg, cfgc, glob, keys, mask, probes);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (f.m) tally_add(&glob[TG_ROUTED_REQ], f.m);
+        tally_u64 dropped = 0;
+        if (recv_info)
+            for (uint32_t s = 0; s < world; s++) dropped += (tally_u64)recv_info[RL_ROUTE_INFO * s + 3] >> 1;
+        if (dropped) tally_add(&glob[TG_ROUTED_DROPPED], dropped);
+    }
 }
 
 // every record free, every counter 0 (rl_tally_enable, a clearing rl_tally_read)

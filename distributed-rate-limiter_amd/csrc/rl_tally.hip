@@ -20,6 +20,17 @@ static hipError_t tally_launch(uint64_t m, const uint64_t* key, const uint32_t* 
     return hipGetLastError();
 }
 
+// k_tally_routed over the merged routed step `io` of bound m_max on stream s
+static hipError_t tally_routed_launch(rl_engine* e, uint64_t m_max, const RoutedIo& io, const int64_t* recv_info,
+                                      uint32_t world, hipStream_t s) {
+    // m_max == 0 (the warm-up): one block that finds nothing to do
+    const int grid = std::max(1, grid_for(m_max, TALLY_BLOCK, TALLY_GRID));
+    k_tally_routed<<<grid, TALLY_BLOCK, 0, s>>>(m_max, io, recv_info, world, (uint32_t)e->h_cfg.size(), e->d_tally_cfg,
+                                                e->d_tally_glob, e->d_tally_keys, e->tally_slots - 1,
+                                                std::min<uint64_t>(e->tally_slots, TALLY_PROBES));
+    return hipGetLastError();
+}
+
 // k_tally_clear: every record free, every counter 0
 static hipError_t tally_clear_launch(TallyKey* keys, uint64_t slots, tally_u64* cfgc, uint64_t cfg_words,
                                      tally_u64* glob, hipStream_t s) {
@@ -58,16 +69,21 @@ extern "C" int rl_tally_enable(rl_engine* e, const rl_tally_opts* o) {
         // an empty launch loads the kernel now, not in front of the first batch
         ok = ok && tally_launch(0, nullptr, nullptr, nullptr, nullptr, 0, e->d_tally_cfg, e->d_tally_glob,
                                 e->d_tally_keys, slots, e->stream) == hipSuccess;
+        // the routed form on a zero count
+        e->tally_slots = slots;
+        const RoutedIo io{nullptr, nullptr, e->d_zero, nullptr, nullptr, e->d_eflags};
+        ok = ok && tally_routed_launch(e, 0, io, nullptr, 0, e->stream) == hipSuccess;
         ok = ok && hipStreamSynchronize(e->stream) == hipSuccess;
     }
     if (!ok) {
+        e->tally_slots = 0;
         (void)hipFree(e->d_tally_keys); (void)hipFree(e->d_tally_cfg); (void)hipFree(e->d_tally_glob);
         e->d_tally_keys = nullptr; e->d_tally_cfg = nullptr; e->d_tally_glob = nullptr;
         return fail(e, RL_ENOMEM, "tally allocation failed");
     }
     e->tally_slots = slots;
     e->tally_cfg_cap = cap;
-    e->tally_batches = e->tally_requests = 0;
+    e->tally_batches = e->tally_requests = e->tally_routed_steps = 0;
     e->tally_on = true;
     return RL_OK;
 }
@@ -155,9 +171,46 @@ extern "C" int rl_tally_read(rl_engine* e, rl_tally_cfg* cfg_out, size_t cfg_cap
         HIPCHK(e, tally_clear_launch(e->d_tally_keys, e->tally_slots, e->d_tally_cfg,
                                      (uint64_t)TALLY_CFG_WORDS * e->tally_cfg_cap, e->d_tally_glob, s));
         HIPCHK(e, hipStreamSynchronize(s));
-        e->tally_batches = e->tally_requests = 0;
+        e->tally_batches = e->tally_requests = e->tally_routed_steps = 0;
     }
     return RL_OK;
+}
+
+// The routed form (include/rl_route.h): one launch on the caller's stream,
+// behind the step's results; like k_tally it touches the tally's own memory
+// only (and re-raises EF_ROUTED_OVER on a count above m_max), so it uses none
+// of the engine's streams and is waited for through side_record's events.
+extern "C" int rl_tally_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                                      const uint32_t* order, const int64_t* server_ms, const rl_route_res* res,
+                                      const int64_t* recv_info, uint32_t world, void* stream) {
+    if (!e || !e->tally_on || m_max > 0xffffffffull) return RL_EINVAL;
+    if (m_max == 0) return RL_OK;
+    if (!count || !recv || !order || !server_ms || !res) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    const RoutedIo io{recv, order, count, server_ms, const_cast<rl_route_res*>(res), e->d_eflags};   // res is only read
+    HIPCHK(e, tally_routed_launch(e, (uint64_t)m_max, io, recv_info, recv_info ? world : 0, s));
+    const int r = side_record(e, s);
+    if (r != RL_OK) return r;
+    e->tally_routed_steps++;
+    return RL_OK;
+}
+
+extern "C" int rl_tally_routed_read(rl_engine* e, rl_tally_routed_info* out) {
+    if (!e || !e->tally_on || !out || out->struct_size < 8) return RL_EINVAL;
+    (void)hipSetDevice(e->device);
+    {
+        const int r = side_wait(e);
+        if (r != RL_OK) return r;
+    }
+    tally_u64 glob[TG_WORDS];
+    HIPCHK(e, hipMemcpyAsync(glob, e->d_tally_glob, sizeof(glob), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    rl_tally_routed_info I{};
+    I.steps = e->tally_routed_steps;
+    I.requests = glob[TG_ROUTED_REQ];
+    I.dropped_requests = glob[TG_ROUTED_DROPPED];
+    return copy_out(out, I);
 }
 
 extern "C" int rl_tally_grid_cap(void) { return TALLY_GRID * TALLY_BLOCK; }

@@ -118,6 +118,12 @@ class rl_tally_info(_Sized):
                                   "unknown_cfg", "bad_codes", "batches", "requests")]
 
 
+class rl_tally_routed_info(_Sized):
+    """include/rl_route.h"""
+    _fields_ = [("struct_size", C.c_uint32), ("pad_", C.c_uint32)] + [
+        (k, C.c_uint64) for k in ("steps", "requests", "dropped_requests")]
+
+
 # rl_tally_cfg / rl_tally_key as numpy records
 TALLY_CFG = np.dtype([("count", np.uint64, 4), ("units", np.uint64, 2)])
 TALLY_KEY = np.dtype([("key_id", np.uint64), ("denied", np.uint64), ("units_denied", np.uint64),
@@ -360,6 +366,9 @@ _sig = {
     "rl_reset_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
     "rl_refund_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
     "rl_charge_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 8),
+    "rl_tally_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 6 + [C.c_uint32, vp]),
+    "rl_hot_routed_device": (C.c_int, [vp, C.c_size_t] + [vp] * 6),
+    "rl_tally_routed_read": (C.c_int, [vp, C.POINTER(rl_tally_routed_info)]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)
@@ -435,11 +444,14 @@ class Hot:
 @dataclass
 class Tally:
     """rl_tally_read: cfg[c] the counters of config c (TALLY_CFG), keys the
-    top throttled keys (TALLY_KEY, most denied first), info the rl_tally_info"""
+    top throttled keys (TALLY_KEY, most denied first), info the rl_tally_info,
+    routed the rl_tally_routed_info of an Engine's read (as it was before a
+    clearing read cleared it)"""
     cfg: np.ndarray
     keys: np.ndarray
     keys_tracked: int
     info: rl_tally_info
+    routed: rl_tally_routed_info | None = None
 
 
 class Engine:
@@ -585,6 +597,35 @@ class Engine:
             raise ValueError("charge_routed_ev needs an event")
         self._routed_op(lib.rl_charge_routed_device, m_max, count_p, recv_p, order_p, sms_p, res_p, stream, None,
                         event_p)
+
+    def tally_routed(self, m_max, count_p, recv_p, order_p, sms_p, res_p, rcnt_p=None, world=0, stream=None):
+        """rl_tally_routed_device: the usage tally of a finished routed decide
+        step, counted on the keys' owner -- the merged batch and its result
+        records, enqueued on `stream` behind the results; rcnt_p (the received
+        info rows of `world` sources, or None) counts the requests dropped at
+        their senders.  The signature of RoutedPipeline's observe= callables"""
+        rc = lib.rl_tally_routed_device(self.h, m_max, count_p, recv_p, order_p, sms_p, res_p, rcnt_p, world, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def hot_routed(self, m_max, count_p, recv_p, order_p, sms_p, res_p, rcnt_p=None, world=0, stream=None):
+        """rl_hot_routed_device: the top keys of a finished routed decide step,
+        counted on the keys' owner (the adds, then the pick, on `stream`).
+        rcnt_p and world are taken and ignored -- dropped requests have no key
+        here -- so that the method is an observe= callable as it stands"""
+        rc = lib.rl_hot_routed_device(self.h, m_max, count_p, recv_p, order_p, sms_p, res_p, stream)
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+
+    def tally_routed_read(self) -> rl_tally_routed_info:
+        """rl_tally_routed_read: the routed tally's own counters -- steps,
+        requests looked at, requests dropped at their senders (zeroed by a
+        clearing tally_read)"""
+        info = rl_tally_routed_info()
+        rc = lib.rl_tally_routed_read(self.h, C.byref(info))
+        if rc != RL_OK:
+            raise EngineError(rc, self.last_error())
+        return info
 
     def decide_device(self, m, key_p, ts_p, n_p, cfg_p, sms_p, dec_p, rem_p, retry_p, reset_p, tok_p,
                       stream=None):
@@ -785,11 +826,12 @@ class Engine:
             raise EngineError(rc, self.last_error())
         cfg = np.zeros(ncfg.value, TALLY_CFG)
         keys = np.zeros(top, TALLY_KEY)
+        routed = self.tally_routed_read()
         rc = lib.rl_tally_read(self.h, _ptr(cfg), cfg.size, C.byref(ncfg), _ptr(keys), top, C.byref(tracked),
                                C.byref(info), 1 if clear else 0)
         if rc != RL_OK:
             raise EngineError(rc, self.last_error())
-        return Tally(cfg, keys[:min(top, tracked.value)], tracked.value, info)
+        return Tally(cfg, keys[:min(top, tracked.value)], tracked.value, info, routed)
 
     def hot_enable(self, hot_min, width=0, key_slots=0, weight=HOT_REQUESTS):
         """rl_hot_enable: allocate the top-keys sketch (width counters per row,

@@ -49,6 +49,113 @@ def owner_of(key: np.ndarray, world: int) -> np.ndarray:
     return ((mix64(key) >> np.uint64(32)) % np.uint64(world)).astype(np.int64)
 
 
+# --- cluster-wide reads of the usage tally and the top keys ----------------------
+#
+# Every rank counts the routed steps it OWNS (rl_tally_routed_device,
+# rl_hot_routed_device), so the ranks' reads are over disjoint key sets and a
+# cluster read is a merge of small lists: `top` records per rank.
+
+_M64 = (1 << 64) - 1
+
+
+def _fields(x):
+    """an info record -- a dict, or a ctypes struct of counters -- as a dict of ints"""
+    if x is None:
+        return {}
+    if isinstance(x, dict):
+        return {k: int(v) for k, v in x.items()}
+    return {k: int(getattr(x, k)) for k, _ in x._fields_ if k not in ("struct_size", "pad_")}
+
+
+def tally_part(t):
+    """one rank's tally read (rl_amd.Tally, or anything with its cfg, keys,
+    info and routed) as a plain dict that travels between ranks"""
+    if isinstance(t, dict):
+        return t
+    return dict(cfg=np.array(t.cfg), keys=np.array(t.keys), info=_fields(t.info),
+                routed=_fields(getattr(t, "routed", None)))
+
+
+def hot_part(h):
+    """one rank's top-keys read (rl_amd.Hot) as a plain dict"""
+    if isinstance(h, dict):
+        return h
+    return dict(keys=np.array(h.keys), info=_fields(h.info))
+
+
+def _sum_fields(dicts, skip=()):
+    out = {}
+    for d in dicts:
+        for k, v in d.items():
+            if k not in skip:
+                out[k] = (out.get(k, 0) + int(v)) & _M64
+    return out
+
+
+def _unite(parts, value_fields, order_field, top):
+    """the parts' key records united by key_id: a key two parts report has its
+    value fields summed (modulo 2^64) and keeps the first part's other fields;
+    ordered by order_field descending, then key id ascending, cut to `top`"""
+    dt = parts[0]["keys"].dtype
+    recs = {}
+    for part in parts:
+        for r in part["keys"]:
+            k = int(r["key_id"])
+            if k in recs:
+                for f in value_fields:
+                    recs[k][f] = (int(recs[k][f]) + int(r[f])) & _M64
+            else:
+                recs[k] = {f: r[f] for f in dt.names}
+    ids = sorted(recs, key=lambda k: (-int(recs[k][order_field]), k))[:max(0, int(top))]
+    out = np.zeros(len(ids), dt)
+    for i, k in enumerate(ids):
+        for f in dt.names:
+            out[f][i] = recs[k][f]
+    return out
+
+
+def merge_tallies(parts, top):
+    """the ranks' tally reads (tally_part dicts or rl_amd.Tally, in rank order)
+    as one: config rows summed modulo 2^64, info fields and the routed info
+    summed, key lists united -- a key id reported by two ranks is summed and
+    keeps the lowest rank's cfg, which cannot happen under the owner partition
+    -- ordered by denied descending, then key id ascending, cut to `top`.
+    -> dict(cfg, keys, keys_tracked, info, routed)"""
+    parts = [tally_part(p) for p in parts]
+    rows = max(p["cfg"].size for p in parts)
+    cfg = np.zeros(rows, parts[0]["cfg"].dtype)
+    with np.errstate(over="ignore"):
+        for p in parts:
+            for f in cfg.dtype.names:
+                cfg[f][:p["cfg"].size] += p["cfg"][f]      # uint64: wraps
+    info = _sum_fields([p["info"] for p in parts])
+    return dict(cfg=cfg, keys=_unite(parts, ("denied", "units_denied"), "denied", top),
+                keys_tracked=info.get("keys_tracked", 0), info=info,
+                routed=_sum_fields([p.get("routed") or {} for p in parts]))
+
+
+_HOT_SAME = ("width", "depth", "hot_min", "weight")
+
+
+def merge_hots(parts, top):
+    """the ranks' top-keys reads (hot_part dicts or rl_amd.Hot, in rank order)
+    as one: keys united, ordered by estimate descending, then key id ascending,
+    cut to `top`; total, skipped, keys_tracked (and key_slots, batches,
+    requests) summed; dropped non-zero if any part's is; width, depth, hot_min
+    and weight must agree on all parts, else ValueError -- estimates of
+    different sketches do not compare.  -> dict(keys, keys_tracked, info)"""
+    parts = [hot_part(p) for p in parts]
+    for f in _HOT_SAME:
+        vals = {p["info"].get(f) for p in parts}
+        if len(vals) > 1:
+            raise ValueError(f"merge_hots: the parts' {f} differ: {sorted(vals, key=str)}")
+    info = _sum_fields([p["info"] for p in parts], skip=_HOT_SAME + ("dropped",))
+    info.update({f: parts[0]["info"][f] for f in _HOT_SAME if f in parts[0]["info"]})
+    info["dropped"] = int(any(p["info"].get("dropped", 0) for p in parts))
+    return dict(keys=_unite(parts, ("estimate",), "estimate", top), keys_tracked=info.get("keys_tracked", 0),
+                info=info)
+
+
 # --- the native routed pipeline (include/rl_route.h) ---------------------------
 
 INFO = 4   # RL_ROUTE_INFO
@@ -143,12 +250,27 @@ class RoutedPipeline:
     allow_all(b, ...) (settle=: Engine.allow_all_settle) checks each request
     against several limiters, all or nothing, wherever their keys live: decide
     step b, the settle on U, and refund step b + 1 packed with ops.pack_sel from
-    the settle's give-backs (include/rl_route.h)."""
+    the settle's give-backs (include/rl_route.h).
+
+    observe= (a list of callables f(m_max, count, recv, order, sms, res, rcnt,
+    world, stream): Engine.tally_routed, Engine.hot_routed) counts every decide
+    step, and the member decide step of allow_all, on the keys' owner: the calls
+    are enqueued on U in the step's result side, after the result all-to-all and
+    the unpack -- the results leave first -- and before the buffer set's ev_done,
+    so the set is not rewritten under them (on a CPU pipeline: inline after the
+    unpack).  Peek, reset, refund and charge steps are not counted, nor are
+    allow_all's give-backs.  Without observe the pipeline issues exactly the
+    calls it issues otherwise.  usage() / top_keys() read the cluster's counts
+    (DESIGN.md §10o)."""
 
     def __init__(self, ops, decide, world, max_batch, device, pg_req=None, pg_res=None, depth=4, exchange=None,
                  staged=False, lookahead=None, ordered=True, decide_ev=None, *, peek=None, peek_ev=None, reset=None,
-                 reset_ev=None, refund=None, refund_ev=None, settle=None, charge=None, charge_ev=None):
+                 reset_ev=None, refund=None, refund_ev=None, settle=None, charge=None, charge_ev=None, observe=None):
         self.ops, self.decide, self.world = ops, decide, world
+        # observe: callables f(m_max, count, recv, order, sms, res, rcnt, world,
+        # stream) run on U over every finished decide step (Engine.tally_routed,
+        # Engine.hot_routed; device pointers)
+        self.observe = list(observe or ())
         # settle(m, first, cfg, n, dec, verdict, g, sel, stream): the sender's
         # settle of allow_all (rl_allow_all_settle_device; device pointers)
         self.settle = settle
@@ -290,7 +412,8 @@ class RoutedPipeline:
                 self._zero_n = torch.zeros(self.max_batch, dtype=torch.int64, device=self.dev)
             n = self._zero_n[:m]
         self._request_side(b, key, ts, n, cfg, call, call_ev)
-        self._pend.append((b, self.slots[b % self.depth], m, dec, rem, retry, reset, call_ev is not None))
+        self._pend.append((b, self.slots[b % self.depth], m, dec, rem, retry, reset, call_ev is not None,
+                           op == OP_DECIDE))
         done = []
         while len(self._pend) > self.lookahead:
             done.append(self._result_side(*self._pend.pop(0)))
@@ -363,7 +486,8 @@ class RoutedPipeline:
         p, sp, U = self._p, self._sp, self.U
         done = self.flush()                       # Res(pending): the same order on every rank
         self._request_side(b, key, ts, n, cfg, call, call_ev)
-        done.append(self._result_side(b, self.slots[b % self.depth], m, dec, rem, retry, reset, call_ev is not None))
+        done.append(self._result_side(b, self.slots[b % self.depth], m, dec, rem, retry, reset, call_ev is not None,
+                                      True))
         with _ctx(U):
             if A["ev_packed"] is not None:
                 U.wait_event(A["ev_packed"])      # the previous call's pack has read g and sel
@@ -377,7 +501,11 @@ class RoutedPipeline:
             done.append(self._result_side(*self._pend.pop(0)))
         return done
 
-    def _result_side(self, b, s, m, dec, rem, retry, reset, by_event):
+    def _result_side(self, b, s, m, dec, rem, retry, reset, by_event, observed=False):
+        """result exchange and unpack of step b on U; observed: a decide step,
+        which the observe= callables then count on its owner -- behind the
+        exchange and the unpack, so the results leave first, and before
+        ev_done, so the buffer set is not rewritten under them"""
         p, sp, U = self._p, self._sp, self.U
         with _ctx(U):
             if by_event:
@@ -390,6 +518,12 @@ class RoutedPipeline:
                 self._ev_res = self._record(U)
             self.ops.unpack(m, p(s["slot"]), p(s["back"] if self.exchange else s["res"]), p(dec), p(rem), p(retry),
                             p(reset), sp(U))
+            if observed and self.observe:
+                recv = s["recv"] if self.exchange else s["send"]
+                rcnt = s["rcnt"] if self.exchange else s["scnt"]
+                for f in self.observe:
+                    f(self.m_max, p(s["count"]), p(recv), p(s["order"]), p(s["sms"]), p(s["res"]), p(rcnt),
+                      self.world, sp(U))
             if U is not None:
                 s["ev_done"] = torch.cuda.Event()
                 s["ev_done"].record(U)
@@ -401,6 +535,33 @@ class RoutedPipeline:
         while self._pend:
             done.append(self._result_side(*self._pend.pop(0)))
         return done
+
+    def _gather(self, read, top, clear, part_of, merge):
+        self.flush()
+        if self.U is not None:
+            self.U.synchronize()      # every observe call has been enqueued on U: the local read sees them all
+        part = part_of(read(top=top, clear=clear))
+        if self.world == 1 and self.pg_res is None:
+            return merge([part], top)
+        parts = [None] * self.world
+        dist.all_gather_object(parts, part, group=self.pg_res)
+        return merge(parts, top)
+
+    def usage(self, read, top=0, clear=False):
+        """the cluster's usage tally (observe=[Engine.tally_routed]; read:
+        Engine.tally_read): a collective -- every rank calls it at the same
+        point.  Issues every deferred result side, waits for U, reads this
+        rank's tally with the caller's `top` (and `clear`), gathers the ranks'
+        reads over pg_res (world 1 without a group: no collective) and returns
+        merge_tallies of them, the same on every rank.  The cluster's `top`
+        most denied keys are among the ranks' local `top`: a key's denials are
+        all on its owner."""
+        return self._gather(read, top, clear, tally_part, merge_tallies)
+
+    def top_keys(self, read, top=0, clear=False):
+        """the cluster's top keys (observe=[Engine.hot_routed]; read:
+        Engine.hot_read): a collective like usage(), merged by merge_hots"""
+        return self._gather(read, top, clear, hot_part, merge_hots)
 
     def run(self, batches, outs, done=None, kinds=None):
         """all batches through the pipeline: batches[b] = (key, ts, n, cfg),

@@ -330,6 +330,57 @@ int rl_charge_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, c
                             const uint32_t* order, const int64_t* server_ms, rl_route_res* res, void* in_stream,
                             void* out_stream, void* done_event);
 
+/* Routed usage tally and top keys: the routed forms of rl_tally_batch_device
+ * and rl_hot_batch_device (include/rl_engine.h),
+ * counted on the key's OWNER GPU.  A key has one owner, so its counts are whole
+ * there: the tally's "tracked completely or not at all" holds per key, hot_min
+ * means what it means on one GPU, every owner's sketch holds only its share of
+ * the keys, and the cluster's top-k is contained in the union of the ranks'
+ * local top-k lists (shard.merge_tallies / merge_hots).
+ *   request p   of a finished decide step: (key, cfg, n) of recv[order[p]] (or
+ *          the RL_ORDER_IDENTITY form) and res[order[p]].decision, p <
+ *          min(m_max, *count) -- the requests the engine gave results; ts, pos
+ *          and the store clock are not used.  The counting rules are those of
+ *          the array forms, the decision being an int64: with a registered cfg,
+ *          a decision outside 0..3 (negative values included) adds one to
+ *          bad_codes (tally) or skipped (top keys) and nothing else.
+ *   drops       a request dropped at its sender never reaches the owner; with
+ *          recv_info (the received info rows, nullable) the tally adds the sum
+ *          over the `world` sources of recv_info[RL_ROUTE_INFO * s + 3] >> 1 to
+ *          dropped_requests.  Only their number is known, not their units.
+ *   streams     enqueued on `stream` (NULL: the engine's stream): one launch
+ *          for the tally, two (the adds, then the pick) for the top keys.  The
+ *          caller guarantees that the step's results are complete on `stream`
+ *          and that recv / res stay unmodified until the stream has passed the
+ *          call.  The calls use neither the replay stream nor the state tables,
+ *          write only the feature's own memory and leave rl_stats and the sticky
+ *          status alone -- except that a count above m_max re-raises
+ *          RL_EOVERFLOW, which the decide of that step raised already.
+ *   status      RL_EINVAL before rl_tally_enable / rl_hot_enable, for m_max
+ *          above 32 bits, and for a null count, recv, order, server_ms or res
+ *          with m_max > 0; m_max == 0 is RL_OK without a launch.
+ *   reads       rl_tally_read / rl_hot_read return the routed and the array
+ *          calls' counts together; rl_tally_info and rl_hot_info keep their
+ *          meaning (batches / requests count array calls only; the sketch's
+ *          total and skipped are device words, so routed calls move them).
+ *          rl_tally_routed_read (synchronous) adds what is the routed form's
+ *          own: steps = calls with m_max > 0 (kept on the host), requests =
+ *          routed requests looked at, dropped_requests as above.  A clearing
+ *          rl_tally_read zeroes all three.
+ * Which steps to count is the caller's choice; shard.RoutedPipeline(observe=)
+ * counts decide steps and the member decide step of a routed AllowAll, not its
+ * give-backs, and no peek, reset, refund or charge step. */
+int rl_tally_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                           const uint32_t* order, const int64_t* server_ms, const rl_route_res* res,
+                           const int64_t* recv_info, uint32_t world, void* stream);
+int rl_hot_routed_device(rl_engine* e, size_t m_max, const uint32_t* count, const rl_route_rec* recv,
+                         const uint32_t* order, const int64_t* server_ms, const rl_route_res* res, void* stream);
+typedef struct rl_tally_routed_info {
+    uint32_t struct_size, pad_;
+    uint64_t steps, requests, dropped_requests;
+} rl_tally_routed_info;
+int rl_tally_routed_read(rl_engine* e, rl_tally_routed_info* out);
+
 /* Routed AllowAll: rl_allow_all_batch (include/rl_engine.h)
  * for members whose keys live on different GPUs.  It is two
  * routed steps, b and b + 1, with a settle on the sender between them and no
